@@ -41,6 +41,12 @@ Roofline objects of the JSON line:
 
 Contract: `python bench.py --gpus N --steps K --warmup W`; N>1 is launched by torch.distributed.run (one rank per GPU).
 Rank 0 prints ONE JSON line (the last line on stdout).
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the line (`metric`, `value`, `unit`,
+`ms_per_step`, `config`, ...).  Everything else -- the roofline objects, the p99 kernel samples, strong scaling beside weak at N>1,
+the host-path and small-batch latencies, the CPU baseline and the parity check against the oracle, the closed-loop verification,
+`closed_loop`, `roofline_cold`, `revisit` -- runs with `--full`.  `--dump-outputs DIR` writes what the timed path returned in its
+last step (picks and scores of that batch; at N>1 also the all-gathered picks) as DIR/<name>.npy, float64.
 """
 from __future__ import annotations
 
@@ -564,7 +570,14 @@ def main() -> None:
     ap.add_argument("--profile-every", type=int, default=8, help="inside the timed region only every Nth pick launch carries HIP events and probe counters (1 = all)")
     ap.add_argument("--p99-samples", type=int, default=1000, help="kernel durations collected for the p99 (beyond the timed region if it has fewer launches)")
     ap.add_argument("--host-path", type=int, default=1000, help="also time N batches through the host-buffer entry point (H2D + kernel + D2H): the pick latency a host caller observes; 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: roofline objects and p99 samples, strong scaling beside weak (N>1), host-path latencies, CPU "
+                         "baseline + parity, closed-loop verification, the closed-loop / cold-index / returning-request sub-runs (off: the timed steps alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the picks and scores of the timed region's last step as DIR/<name>.npy (float64; at most 64 MB, a fixed sample beyond)")
     args = ap.parse_args()
+    if args.group and args.dump_outputs:
+        ap.error("--dump-outputs covers the torch.distributed path, not --group")
 
     import torch
 
@@ -609,14 +622,16 @@ def main() -> None:
     # --steps 20: 0.4 ms on one GPU, 50 us at ideal 8-GPU strong scaling) measures one collective's latency and one fence, not the
     # path (one-GPU dry run of both at --steps 20 in profiles/r03_y_short_runs.txt).
     modes = ["single"] if not use_dist else (["weak", "strong"] if args.scaling == "both" else [args.scaling])
+    if not args.full:
+        modes = modes[:1]            # (strong scaling is timed beside weak scaling with --full)
     results = {}
     cl_info = cl_state = None
     for mode in modes:
         run.setup(mode, args.gather_every if mode != "weak" else min(args.gather_every, WEAK_BUCKET))
         age = None
         if args.closed_loop:
-            cl_info = closed_loop_verify(run, wl, args)
-            state = cl_state = {"epoch": cl_info["epoch"]}
+            cl_info = closed_loop_verify(run, wl, args) if args.full else None
+            state = cl_state = {"epoch": cl_info["epoch"] if cl_info else 1}
 
             def age(i, state=state):      # stream-ordered: behind the inserts of this step, ahead of the next pick
                 if (i + 1) % args.age_every == 0:
@@ -629,11 +644,12 @@ def main() -> None:
                              bucket=run.ring.gather_every, pack16=run.pack16,
                              value=(world if mode == "weak" else 1) * R * args.steps / elapsed, ms_per_step=1e3 * elapsed / args.steps)
         if mode == modes[0]:
-            extra_ms = run.more_kernel_samples(len(kern_ms), args.p99_samples) if not args.closed_loop else np.zeros(0)
+            # what the timed region's last step returned (before any launch behind it)
             picks, scores = run.last_outputs()
             last_batch, lo, n_mine = run.last_batch, run.lo, run.n_mine
             gathered = run.check_gather()
             last_step = run.step_no - 1
+            extra_ms = run.more_kernel_samples(len(kern_ms), args.p99_samples) if args.full and not args.closed_loop else np.zeros(0)
         else:
             run.check_gather()
     run.pk.profile(False)
@@ -698,6 +714,7 @@ def main() -> None:
                                              "buckets": int(bl.size), "batches_per_bucket": int(max(res["bucket_batches"])),
                                              "definition": "device time from the start of the (first) launch that scores a gather bucket's batches on this rank to the end of the "
                                                            "all-gather that hands their picks to every rank (events on the compute and the collective stream, rank 0, timed region)"}
+    if rank == 0 and args.full:
         k_timed = res["kern_ms"]
         k_all = np.concatenate([k_timed, extra_ms]) if extra_ms.size else k_timed
         # launch duration: the sampled launches of the timed region plus the every-launch samples taken behind it (same launch pattern)
@@ -899,7 +916,7 @@ def main() -> None:
     # The path's STEADY STATE in the line the driver runs (rank 0, N = 1, headline runs): pick -> the index learns the picks -> next,
     # different batch, ageing every other step -- its first generations verified against the oracle at full size -- and the same loop
     # through the pipelined host entry points (EPPK_PICK_LEARN).  A context of its own (16 Mi index slots); ~3 s.
-    if rank == 0 and world == 1 and (headline or args.closed_loop_leg) and not args.closed_loop and not use_dist and not args.no_closed_loop_leg:
+    if args.full and rank == 0 and world == 1 and (headline or args.closed_loop_leg) and not args.closed_loop and not use_dist and not args.no_closed_loop_leg:
         try:
             cl = closed_loop_leg(pkg, torch, args, wl, batches)
             out["closed_loop"] = cl["closed_loop"]
@@ -910,20 +927,22 @@ def main() -> None:
             out["closed_loop"] = {"error": repr(e)}
 
     # roofline_cold: the same kernel on an index that does not fit the caches (rank 0, N=1, headline runs only)
-    if rank == 0 and world == 1 and headline and not args.no_cold_ref and not use_dist:
+    if args.full and rank == 0 and world == 1 and headline and not args.no_cold_ref and not use_dist:
         try:
             out["roofline_cold"] = cold_reference(pkg, torch, args, khash)
         except Exception as e:  # never lose the headline line to the reference sub-run
             out["roofline_cold"] = {"error": repr(e)}
 
     # revisit: batches of RETURNING requests (rank 0, N = 1, headline runs)
-    if rank == 0 and world == 1 and (headline or args.revisit_leg) and not args.closed_loop and not use_dist and not args.no_revisit_leg and wl.B:
+    if args.full and rank == 0 and world == 1 and (headline or args.revisit_leg) and not args.closed_loop and not use_dist and not args.no_revisit_leg and wl.B:
         try:
             out["revisit"] = revisit_leg(pkg, torch, args, wl, batches)
         except Exception as e:  # never lose the headline line to a sub-run
             out["revisit"] = {"error": repr(e)}
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"picks": picks, "scores": scores, **({"gathered_picks": gathered} if gathered is not None else {})})
         steady_state_into_config(out)
         # RCCL writes a version banner through C stdio, which a pipe buffers until exit: push it out first so that the JSON
         # line is the last thing on stdout
@@ -936,6 +955,24 @@ def main() -> None:
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """DIR/<name>.npy of every array as float64 (an int32 pick is exact in it).  An array too large for its share of DUMP_MAX_BYTES is
+    replaced by a fixed, seeded sample of its elements (flattened), with the sampled positions beside it as DIR/<name>_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_MAX_BYTES // (8 * 2 * max(1, len(arrays)))        # elements per file (an array and, when sampled, its index)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, cap, replace=False))
+            np.save(os.path.join(out_dir, f"{name}_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.astype(np.float64))
 
 
 CONFIG_MAX_KEYS = 20     # the driver's stored record keeps about this many SCALAR `config` keys and no nested objects (BENCH_r05.json: 22)

@@ -26,7 +26,7 @@ else
   mkdir -p gpurun_out
   for round in 1 2; do
     for so in ab/*.so; do
-      EPPK_LIB=$PWD/$so python bench.py --steps 100 --warmup 10 --no-cpu-baseline "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$so', 'kernel_ms=%.4f'%d['roofline']['kernel_avg_ms'], 'Mdec/s=%.1f'%(d['value']/1e6))"
+      EPPK_LIB=$PWD/$so python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$so', 'kernel_ms=%.4f'%d['roofline']['kernel_avg_ms'], 'Mdec/s=%.1f'%(d['value']/1e6))"
     done
   done | tee gpurun_out/ab.txt
 fi

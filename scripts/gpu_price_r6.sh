@@ -9,7 +9,7 @@ for lib in base onelist; do
   echo "== $lib: new / returning 64k batch (scripts/revisit_probe.py)"
   timeout 200 python scripts/revisit_probe.py 65536 2>&1 | tail -2 | tee $OUT/revisit_$lib.txt
   echo "== $lib: headline + cold"
-  timeout 300 python bench.py --steps 50 --warmup 10 --no-cpu-baseline --host-path 0 --no-closed-loop-leg --no-revisit-leg --p99-samples 0 --inflight 1 > $OUT/bench_$lib.json 2> $OUT/bench_$lib.err
+  timeout 300 python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --host-path 0 --no-closed-loop-leg --no-revisit-leg --p99-samples 0 --inflight 1 > $OUT/bench_$lib.json 2> $OUT/bench_$lib.err
   python - $OUT/bench_$lib.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -7,6 +7,7 @@ import io
 import json
 import os
 import sys
+import types
 from contextlib import redirect_stdout
 
 import numpy as np
@@ -144,12 +145,8 @@ def _fake_picker_class(pkg, orc, log):
     return FakePicker
 
 
-@pytest.mark.parametrize("argv", [["--force-dist", "--steps", "11", "--warmup", "3", "--p99-samples", "40"],
-                                  ["--force-dist", "--steps", "8", "--warmup", "8", "--gather-every", "1", "--inflight", "1", "--scaling", "weak"],
-                                  ["--steps", "5", "--warmup", "2", "--batches", "3"],
-                                  ["--steps", "4", "--warmup", "1", "--batches", "2", "--revisit-leg"],
-                                  ["--steps", "6", "--warmup", "2", "--batches", "4", "--closed-loop", "--cl-slots", "4096", "--cl-verify", "3"]])
-def test_bench_control_flow_on_cpu(pkg, orc, monkeypatch, argv):
+def _run_bench_on_cpu(pkg, orc, monkeypatch, argv):
+    """bench.main() under `argv` with the CPU stand-ins; returns (the JSON line, the picker's call log)."""
     import torch
     import torch.distributed as dist
     sys.path.insert(0, ROOT)
@@ -171,10 +168,7 @@ def test_bench_control_flow_on_cpu(pkg, orc, monkeypatch, argv):
     monkeypatch.setenv("MASTER_PORT", str(_free_port()))
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         monkeypatch.delenv(k, raising=False)
-    base = ["bench.py", "--config", "3", "--requests", "96", "--host-path", "3"]
-    if "--p99-samples" not in argv:
-        base += ["--p99-samples", "0"]
-    monkeypatch.setattr(sys, "argv", base + argv)
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
     out = io.StringIO()
     try:
         with redirect_stdout(out):
@@ -183,7 +177,19 @@ def test_bench_control_flow_on_cpu(pkg, orc, monkeypatch, argv):
         if dist.is_initialized():
             dist.destroy_process_group()
     lines = [ln for ln in out.getvalue().splitlines() if ln.strip()]
-    d = json.loads(lines[-1])                                           # the JSON line is the last thing on stdout
+    return json.loads(lines[-1]), log                                  # the JSON line is the last thing on stdout
+
+
+@pytest.mark.parametrize("argv", [["--force-dist", "--steps", "11", "--warmup", "3", "--p99-samples", "40"],
+                                  ["--force-dist", "--steps", "8", "--warmup", "8", "--gather-every", "1", "--inflight", "1", "--scaling", "weak"],
+                                  ["--steps", "5", "--warmup", "2", "--batches", "3"],
+                                  ["--steps", "4", "--warmup", "1", "--batches", "2", "--revisit-leg"],
+                                  ["--steps", "6", "--warmup", "2", "--batches", "4", "--closed-loop", "--cl-slots", "4096", "--cl-verify", "3"]])
+def test_bench_control_flow_on_cpu(pkg, orc, monkeypatch, argv):
+    base = ["--full", "--config", "3", "--requests", "96", "--host-path", "3"]
+    if "--p99-samples" not in argv:
+        base += ["--p99-samples", "0"]
+    d, log = _run_bench_on_cpu(pkg, orc, monkeypatch, base + argv)
     closed = "--closed-loop" in argv
     # `config`: at most 20 scalar keys (what the driver's stored record keeps), the workload first; the rest is in `config_detail`
     assert 5 <= len(d["config"]) <= 20 and all(not isinstance(v, (dict, list)) for v in d["config"].values()), d["config"]
@@ -242,6 +248,54 @@ def test_bench_control_flow_on_cpu(pkg, orc, monkeypatch, argv):
             assert d["config_detail"]["distinct_batches"] == 3
 
 
+
+@pytest.mark.parametrize("extra", [[], ["--force-dist"]])
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(pkg, orc, monkeypatch, tmp_path, extra):
+    """Without --full a run is its timed steps alone: warm-up + steps launches and nothing else, none of the side objects in the line.
+    --dump-outputs writes what the last timed step returned -- the oracle's picks and scores of that step's batch -- identically run
+    after run."""
+    import bench
+    steps, warmup, nb = 7, 2, 3
+    argv = ["--config", "3", "--requests", "96", "--steps", str(steps), "--warmup", str(warmup), "--batches", str(nb)] + extra
+    files = []
+    for i in range(2):
+        d, log = _run_bench_on_cpu(pkg, orc, monkeypatch, argv + ["--dump-outputs", str(tmp_path / f"run{i}")])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config"):
+            assert key in d, key
+        assert d["steps"] == steps and d["warmup"] == warmup and d["unit"] == "decisions/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+        assert abs(d["value"] - 96 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        for key in ("roofline", "cpu_baseline", "parity", "host_path", "closed_loop", "roofline_closed_loop", "roofline_cold", "revisit", "strong"):
+            assert key not in d, key
+        assert sum(1 for e in log if e[0] == "pick") == steps + warmup
+        names = sorted(os.listdir(tmp_path / f"run{i}"))
+        assert names == (["gathered_picks.npy", "picks.npy", "scores.npy"] if extra else ["picks.npy", "scores.npy"])
+        files.append({n: open(tmp_path / f"run{i}" / n, "rb").read() for n in names})
+    assert files[0] == files[1]
+    wl = pkg.workload.make_workload(3, R=96)
+    last = bench.make_batches(pkg, wl, types.SimpleNamespace(config=3), nb)[(steps + warmup - 1) % nb]
+    oix = orc.OracleIndex()
+    oix.insert(wl.index_hashes, wl.index_pods)
+    op, osc, _ = orc.pick_batch(wl.chain, wl.pods, oix, last, wl.B)
+    picks, scores = np.load(tmp_path / "run0" / "picks.npy"), np.load(tmp_path / "run0" / "scores.npy")
+    assert picks.dtype == scores.dtype == np.float64 and picks.shape == scores.shape == (96,)
+    assert np.array_equal(picks, op.astype(np.float64)) and np.array_equal(scores.view(np.uint64), osc.astype(np.float64).view(np.uint64))
+    if extra:
+        assert np.array_equal(np.load(tmp_path / "run0" / "gathered_picks.npy"), picks[None, :])
+
+
+def test_bench_dump_outputs_samples_beyond_its_budget(tmp_path, monkeypatch):
+    """An output larger than its share of the 64 MB is written as a fixed, seeded sample, with the sampled positions beside it."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8 * 2 * 2 * 100)          # 100 elements per file for two arrays
+    a, b = np.arange(1000, dtype=np.int32), np.linspace(0.0, 1.0, 50)
+    for run in ("x", "y"):
+        bench.dump_outputs(str(tmp_path / run), {"a": a, "b": b})
+    assert sorted(os.listdir(tmp_path / "x")) == ["a.npy", "a_index.npy", "b.npy"]
+    idx, sa = np.load(tmp_path / "x" / "a_index.npy"), np.load(tmp_path / "x" / "a.npy")
+    assert idx.size == sa.size == 100 and np.array_equal(sa, a[idx.astype(np.int64)].astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "x" / "b.npy"), b)
+    assert all(open(tmp_path / "x" / n, "rb").read() == open(tmp_path / "y" / n, "rb").read() for n in os.listdir(tmp_path / "x"))
+
 def _bench_worker(rank, world, port, outdir, extra_args=("--batches", "5"), requests=64):
     """One rank of a world-size-2 dry run: the same stand-ins, patched by hand (no pytest fixtures in a spawned process)."""
     sys.path.insert(0, ROOT)
@@ -259,7 +313,7 @@ def _bench_worker(rank, world, port, outdir, extra_args=("--batches", "5"), requ
     dist.init_process_group = lambda backend=None, device_id=None, **k: real_init("gloo", rank=rank, world_size=world)
     log = []
     pkg.BatchedPicker = _fake_picker_class(pkg, orc, log)
-    sys.argv = ["bench.py", "--gpus", str(world), "--config", "3", "--requests", str(requests), "--steps", "10", "--warmup", "3", "--p99-samples", "0",
+    sys.argv = ["bench.py", "--full", "--gpus", str(world), "--config", "3", "--requests", str(requests), "--steps", "10", "--warmup", "3", "--p99-samples", "0",
                 *extra_args]
     out = io.StringIO()
     with redirect_stdout(out):

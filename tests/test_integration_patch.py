@@ -1,15 +1,26 @@
 """The Go side ships as a patch against the reference tree (integration/): it must apply cleanly to the reference's own files.
-(Uncompiled: no Go toolchain in this image.  Needs /root/reference, so it runs in the build container only.)"""
+(Uncompiled: no Go toolchain in this image.)  What the checks need of the reference tree is recorded as digests in
+tests/golden/reference_snapshot.json (tests/golden/extract_reference_snapshot.py), so they run without it."""
+import hashlib
+import importlib.util
+import json
 import os
 import shutil
 import subprocess
-
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PATCH = os.path.join(ROOT, "integration", "0001-lwepp-gpu-endpoint-picker.patch")
 REF = "/root/reference"
 FILES = ["pkg/lwepp/handlers/server.go", "pkg/lwepp/server/options.go", "pkg/lwepp/server/runserver.go", "cmd/lwepp/main.go", "lwepp.Dockerfile"]
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+SNAPSHOT = json.load(open(os.path.join(GOLDEN, "reference_snapshot.json")))
+
+
+def _snapshot_tool():
+    spec = importlib.util.spec_from_file_location("extract_reference_snapshot", os.path.join(GOLDEN, "extract_reference_snapshot.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
 
 
 def test_patch_names_only_the_picker_seam():
@@ -35,8 +46,27 @@ def test_go_pod_row_matches_the_c_struct():
 
 
 def test_patch_applies_to_the_reference(tmp_path):
+    """Every hunk's preimage (its context and removed lines) is the reference's text at the hunk's own position -- what applying it
+    without fuzz or offset takes -- by the digests reference_snapshot.json records of the reference's lines there; the files it creates
+    are new to the reference; server.go keeps the reference's constructor beside the new one.  With a reference checkout at REF the
+    patch is also applied to it with patch(1), and the snapshot must match its files."""
+    tool = _snapshot_tool()
+    modified, created = tool.patch_hunks(open(PATCH).read())
+    assert sorted(modified) == sorted(FILES) and sorted(created) == SNAPSHOT["absent"]
+    for path, hunks in modified.items():
+        rec = SNAPSHOT["files"][path]
+        assert [[a, b, tool.digest_lines(tool.preimage(body))] for a, b, body in hunks] == rec["hunks"], f"{path}: a hunk no longer matches the reference"
+        assert all(a - 1 + b <= rec["lines"] for a, b, _ in hunks)
+    server = [ln for _, _, body in modified["pkg/lwepp/handlers/server.go"] for ln in body]
+    ctor = "func NewStreamingServer(datastore Datastore) *StreamingServer"
+    assert SNAPSHOT["contains"]["pkg/lwepp/handlers/server.go"][ctor] and not any(ln.startswith("-") and ctor in ln for ln in server)
+    assert any(ln.startswith("+") and "NewStreamingServerWithPicker" in ln for ln in server)
+    # the reference's own tests keep compiling against the unchanged constructor
+    assert SNAPSHOT["contains"]["pkg/lwepp/handlers/request_test.go"]["NewStreamingServer(ds)"]
     if not os.path.isdir(REF) or shutil.which("patch") is None:
-        pytest.skip("needs /root/reference and patch(1)")
+        return
+    for path, rec in SNAPSHOT["files"].items():
+        assert hashlib.sha256(open(os.path.join(REF, path), "rb").read()).hexdigest() == rec["sha256"], f"{path}: reference_snapshot.json is stale"
     for f in FILES:
         os.makedirs(os.path.dirname(tmp_path / f), exist_ok=True)
         shutil.copy(os.path.join(REF, f), tmp_path / f)

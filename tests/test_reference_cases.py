@@ -48,10 +48,15 @@ def _candidates_both(pkg, orc, endpoints, filt):
 
 
 def test_fixture_is_current_when_the_reference_is_present():
-    """In the build container the committed JSON must be exactly what the extractor produces from the reference file."""
-    if not os.path.exists(REF_FILE):
-        pytest.skip("no /root/reference on this box: the committed fixture is all there is")
-    assert hashlib.sha256(open(REF_FILE, "rb").read()).hexdigest() == DOC["source_sha256"]
+    """The committed JSON was cut out of the reference file that golden/reference_snapshot.json records (the snapshot the integration
+    patch is checked against): same digest, every case within its lines.  With the reference file at hand, its own digest must match."""
+    snap = json.load(open(os.path.join(HERE, "golden", "reference_snapshot.json")))["files"][DOC["source"]]
+    assert snap["sha256"] == DOC["source_sha256"] and len(CASES) == len(DOC["cases"])
+    for c in DOC["cases"]:
+        lo, hi = c["source_lines"]
+        assert c["name"].startswith("TestHandleRequestHeaders_") and 1 <= lo <= hi <= snap["lines"], c["name"]
+    if os.path.exists(REF_FILE):
+        assert hashlib.sha256(open(REF_FILE, "rb").read()).hexdigest() == DOC["source_sha256"]
     assert len(DOC["cases"]) >= 14
 
 
