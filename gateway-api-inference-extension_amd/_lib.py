@@ -26,6 +26,7 @@ SYMBOLS = [
     "eppk_addr_fingerprint", "eppk_subset_entries", "eppk_snapshot_set_addresses", "eppk_subset_masks_device", "eppk_subset_masks",
     "eppk_pick_batch_subset", "eppk_pick_batch_candidates_device",
     "eppk_launch_status", "eppk_pick_random_topk", "eppk_pick_random_topk_device", "eppk_set_assumed_load",
+    "eppk_pick_weighted_random", "eppk_pick_weighted_random_device", "eppk_group_pick_weighted_random",
     "eppk_group_create", "eppk_group_destroy", "eppk_group_last_error", "eppk_group_size", "eppk_group_ctx", "eppk_group_ranks_seen",
     "eppk_group_set_min_shard", "eppk_group_snapshot_publish", "eppk_group_index_clear", "eppk_group_index_insert",
     "eppk_group_index_remove_pod", "eppk_group_index_advance_epoch", "eppk_group_index_evict_older", "eppk_group_pick_batch",
@@ -123,6 +124,8 @@ def load_library() -> C.CDLL:
     lib.eppk_launch_status.argtypes = [vp, C.POINTER(u32)]
     lib.eppk_pick_random_topk.argtypes = [vp, vp, u32, vp, u32, u64, vp, vp]
     lib.eppk_pick_random_topk_device.argtypes = [vp, vp, u32, vp, u32, u64, vp, vp, vp]
+    lib.eppk_pick_weighted_random.argtypes = [vp, vp, u32, vp, u32, u64, vp, vp]
+    lib.eppk_pick_weighted_random_device.argtypes = [vp, vp, u32, vp, u32, u64, vp, vp, vp]
     lib.eppk_set_assumed_load.argtypes = [vp, u32]
     lib.eppk_group_create.argtypes = [C.POINTER(Cfg), C.POINTER(i32), u32, u32, C.POINTER(vp)]
     lib.eppk_group_destroy.argtypes = [vp]
@@ -146,6 +149,7 @@ def load_library() -> C.CDLL:
     lib.eppk_group_index_trim_pods.argtypes = [vp, u32, C.POINTER(u64)]
     lib.eppk_group_pick_topk.argtypes = [vp, vp, u32, vp, u32, vp, vp]
     lib.eppk_group_pick_random_topk.argtypes = [vp, vp, u32, vp, u32, u64, vp, vp]
+    lib.eppk_group_pick_weighted_random.argtypes = [vp, vp, u32, vp, u32, u64, vp, vp]
     lib.eppk_group_pick_stage_buffers.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(vp)]
     lib.eppk_group_pick_stage_begin.argtypes = [vp, u32, u32, C.c_int, u32]
     lib.eppk_group_pick_stage_end.argtypes = [vp, u32, vp, vp]

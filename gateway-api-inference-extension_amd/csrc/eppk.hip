@@ -338,9 +338,9 @@ KIndex make_kindex(const eppk_ctx* c) {
 // The pick kernels are instantiated in six translation units (eppk_pick_inst.hip.h: one per lane-word type and counter-plane
 // count) so that the build compiles them in parallel; each exports one look-up function.
 
-const void* pick_kernel_ptr(const eppk_ctx* c, bool fast, bool masked, bool topk) {
+const void* pick_kernel_ptr(const eppk_ctx* c, bool fast, bool masked, bool topk, bool wrand = false) {
   eppk::PickVariant v{};
-  v.fast = fast; v.masked = masked; v.topk = topk;
+  v.fast = fast; v.masked = masked; v.topk = topk; v.wrand = wrand;
   v.big = c->slots != 0 && c->index_bytes >= (1ull << 32);   // index of 4 GiB and more: rows through wave-uniform 64-bit bases
   v.has_l = c->has_l; v.has_p = c->has_p; v.p_first = c->p_first; v.gen = c->gen;
   const bool six = c->npl == 6;
@@ -595,6 +595,36 @@ int launch_pick(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t
     c->fixed_bytes += (uint64_t)c->n_pods * sizeof(eppk_pod_row) + (uint64_t)n_reqs * ((uint64_t)c->stride + 4u);
     c->launches++;
   }
+  return EPPK_OK;
+}
+
+// Picker "weighted-random" (SEMANTICS.md §3c): pick_wrand_kernel, one wavefront per request over every candidate, k rounds;
+// d_pick / d_score hold n_reqs * k entries.  r0 = batch index of the first request (the rule hashes it).  1024-thread workgroups
+// when their LDS fits (queue / kv / leading terms per pod, a prefix-ratio table and 64 lane words per wavefront), else 512.
+int launch_wrand(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_mask, int32_t* d_pick, double* d_score, hipStream_t st,
+                 uint32_t k, uint64_t seed, uint32_t r0) {
+  const void* fn = pick_kernel_ptr(c, false, d_mask != nullptr, false, true);
+  KSnap sn = make_ksnap(c);
+  KIndex ix = make_kindex(c);
+  KChain ch = c->kchain;
+  uint32_t pwn = c->pwn;
+  auto lds_of = [&](uint32_t wpb) { return (size_t)sn.J * 64u * 20u + (size_t)wpb * pwn * 8u + (size_t)wpb * 64u * (size_t)c->lw_bytes; };
+  uint32_t threads = 1024u;
+  if (lds_of(threads / 64u) > c->max_lds) threads = 512u;
+  const uint32_t wpb = threads / 64u;
+  const size_t lds = lds_of(wpb);
+  int occ_per_cu = 1;
+  { const int rco = occupancy_of(c, fn, threads, lds, &occ_per_cu); if (rco) return rco; }
+  uint32_t grid = (n_reqs + wpb - 1) / wpb;
+  const uint32_t cap = (uint32_t)c->num_cu * (uint32_t)occ_per_cu;
+  if (grid > cap) grid = cap;
+  if (grid < 1) grid = 1;
+  const uint8_t* reqs8 = (const uint8_t*)d_reqs;
+  uint32_t stride = c->stride;
+  void* args[] = {&sn, &ix, &ch, &reqs8, &stride, &n_reqs, &pwn, &d_mask, &d_pick, &d_score, &k, &seed, &r0};
+  HIPCHK(c, hipExtLaunchKernel(fn, dim3(grid), dim3(threads), args, lds, st, nullptr, nullptr, 0));
+  c->last_done = nullptr;
+  c->last_stream = st;
   return EPPK_OK;
 }
 
@@ -956,8 +986,9 @@ int resident_pick(eppk_ctx* c, uint32_t n_reqs, int32_t* out_pick, double* out_s
 //   k == 1, !random   the pick                         (d_pick / d_score: n entries)
 //   k  > 1, !random   ordered fallbacks                (n * k entries; the request's pick is entry 0 of its list)
 //   random            picker "random-top-k" (§3b)      (n entries), r0 = batch index of the first request (the rule hashes it)
+//   wrand             picker "weighted-random" (§3c)   (n * k entries; `random` false), r0 as above
 int run_pick(eppk_ctx* c, const uint8_t* d_reqs, uint32_t n_reqs, const uint64_t* d_mask, int32_t* d_pick, double* d_score, hipStream_t st,
-             uint32_t k, bool random, uint64_t seed, uint32_t r0, uint32_t* d_learn = nullptr, bool* wrote_learn = nullptr) {
+             uint32_t k, bool random, uint64_t seed, uint32_t r0, uint32_t* d_learn = nullptr, bool* wrote_learn = nullptr, bool wrand = false) {
   bool all_wrote = d_learn != nullptr;       // (learn words: valid only if EVERY launch of the batch wrote its part)
   { const int rcf = learn_fence(c, st); if (rcf) return rcf; }     // (the index an earlier EPPK_PICK_LEARN batch leaves behind)
   const uint32_t E = c->assumed_epochs;
@@ -980,7 +1011,11 @@ int run_pick(eppk_ctx* c, const uint8_t* d_reqs, uint32_t n_reqs, const uint64_t
     int32_t* pick = d_pick + (size_t)lo * ok;
     double* score = d_score ? d_score + (size_t)lo * ok : nullptr;
     int rc;
-    if (random) {
+    if (wrand) {
+      rc = launch_wrand(c, reqs, cnt, mask, pick, score, st, k, seed, r0 + lo);
+      if (rc) return rc;
+      all_wrote = false;
+    } else if (random) {
       rc = launch_pick(c, reqs, cnt, mask, c->d_rs_pick, c->d_rs_score, st, k);
       if (rc) return rc;
       hipLaunchKernelGGL(random_select_kernel, dim3((cnt + 255u) / 256u), dim3(256), 0, st, (const int32_t*)c->d_rs_pick, (const double*)c->d_rs_score,
@@ -2593,6 +2628,62 @@ int eppk_pick_random_topk(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const 
   return EPPK_OK;
 }
 
+// ---- picker "weighted-random" (SEMANTICS.md §3c) ---------------------------------------------------------------------
+
+int eppk_pick_weighted_random_device(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, uint32_t k, uint64_t seed,
+                                     int32_t* d_out_pick, double* d_out_score, void* stream) {
+  if (!c || ((!d_reqs || !d_out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_weighted_random_device: null argument");
+  if (k < 1 || k > EPPK_MAX_TOPK) return fail(c, EPPK_ERR_ARG, "eppk_pick_weighted_random_device: k out of range (1..8)");
+  if (!c->have_snapshot) return fail(c, EPPK_ERR_NO_SNAPSHOT, "eppk_pick_weighted_random_device: no snapshot published");
+  if (n_reqs == 0) return EPPK_OK;
+  if ((uint64_t)n_reqs * c->stride >= (1ull << 31)) return fail(c, EPPK_ERR_LIMIT, "eppk_pick_weighted_random_device: batch of 2 GiB and more (split it)");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  return run_pick(c, (const uint8_t*)d_reqs, n_reqs, d_cand_mask, d_out_pick, d_out_score, st, k, false, seed, 0u, nullptr, nullptr, true);
+}
+
+int eppk_pick_weighted_random(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, uint64_t seed, int32_t* out_pick,
+                              double* out_score) {
+  if (!c || ((!reqs || !out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_weighted_random: null argument");
+  if (k < 1 || k > EPPK_MAX_TOPK) return fail(c, EPPK_ERR_ARG, "eppk_pick_weighted_random: k out of range (1..8)");
+  if (!c->have_snapshot) return fail(c, EPPK_ERR_NO_SNAPSHOT, "eppk_pick_weighted_random: no snapshot published");
+  if (n_reqs > c->cfg.max_batch) return fail(c, EPPK_ERR_LIMIT, "eppk_pick_weighted_random: n_reqs > max_batch");
+  if (n_reqs == 0) return EPPK_OK;
+  int rc = validate_rows(c, "eppk_pick_weighted_random", reqs, n_reqs);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const size_t J = (c->n_pods + 63u) / 64u;
+  if (cand_mask && !J) {
+    for (size_t i = 0; i < (size_t)n_reqs * k; ++i) { out_pick[i] = EPPK_NO_PICK; if (out_score) out_score[i] = 0.0; }
+    return EPPK_OK;
+  }
+  if (n_reqs <= c->zero_copy_max && (size_t)n_reqs * k <= c->cfg.max_batch) {
+    // zero-copy (small batch): the kernel reads the pinned rows and writes the n x k lists into the pinned results (max_batch entries each)
+    rc = ensure_host_staging(c, cand_mask != nullptr);
+    if (rc) return rc;
+    if (reqs != c->h_reqs) std::memcpy(c->h_reqs, reqs, (size_t)n_reqs * c->stride);
+    if (cand_mask && cand_mask != c->h_mask) std::memcpy(c->h_mask, cand_mask, (size_t)n_reqs * J * 8u);
+    rc = run_pick(c, (const uint8_t*)c->h_reqs_dev, n_reqs, cand_mask ? c->h_mask_dev : nullptr, c->h_pick_dev, c->h_score_dev, c->stream, k, false, seed, 0u,
+                  nullptr, nullptr, true);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(out_pick, c->h_pick, (size_t)n_reqs * k * 4u);
+    if (out_score) std::memcpy(out_score, c->h_score, (size_t)n_reqs * k * 8u);
+    return EPPK_OK;
+  }
+  // the buffers of the ordered fallbacks (max_batch x EPPK_MAX_TOPK entries)
+  { const int rct = topk_ensure(c, cand_mask != nullptr); if (rct) return rct; }
+  HIPCHK(c, hipMemcpyAsync(c->d_tk_reqs, reqs, (size_t)n_reqs * c->stride, hipMemcpyHostToDevice, c->stream));
+  if (cand_mask) HIPCHK(c, hipMemcpyAsync(c->d_tk_mask, cand_mask, (size_t)n_reqs * J * 8u, hipMemcpyHostToDevice, c->stream));
+  rc = run_pick(c, (const uint8_t*)c->d_tk_reqs, n_reqs, cand_mask ? c->d_tk_mask : nullptr, c->d_tk_pick, c->d_tk_score, c->stream, k, false, seed, 0u,
+                nullptr, nullptr, true);
+  if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(out_pick, c->d_tk_pick, (size_t)n_reqs * k * 4u, hipMemcpyDeviceToHost, c->stream));
+  if (out_score) HIPCHK(c, hipMemcpyAsync(out_score, c->d_tk_score, (size_t)n_reqs * k * 8u, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return EPPK_OK;
+}
+
 int eppk_set_assumed_load(eppk_ctx* c, uint32_t epochs) {
   if (!c) return EPPK_ERR_ARG;
   if (epochs > 65536u) return fail(c, EPPK_ERR_LIMIT, "eppk_set_assumed_load: more than 65536 epochs per batch");
@@ -3115,8 +3206,9 @@ struct Shards {
 };
 
 // ordered fallbacks / picker "random-top-k" over the group: sharded by request like eppk_group_pick_batch, every member busy at once
+// (wrand: picker "weighted-random", k entries per request; `random` false)
 int group_topk(eppk_group* g, const char* who, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, bool random, uint64_t seed,
-               int32_t* out_pick, double* out_score) {
+               int32_t* out_pick, double* out_score, bool wrand = false) {
   if (!g || ((!reqs || !out_pick) && n_reqs)) return gfail(g, EPPK_ERR_ARG, std::string(who) + ": null argument");
   if (k < 1 || k > EPPK_MAX_TOPK) return gfail(g, EPPK_ERR_ARG, std::string(who) + ": k out of range (1..8)");
   if (n_reqs > g->max_batch) return gfail(g, EPPK_ERR_LIMIT, std::string(who) + ": n_reqs > max_batch");
@@ -3153,7 +3245,8 @@ int group_topk(eppk_group* g, const char* who, const void* reqs, uint32_t n_reqs
         (cand_mask && hipMemcpyAsync(m->d_tk_mask, g->h_tk_mask + (size_t)lo * J, (size_t)cnt * J * 8u, hipMemcpyHostToDevice, m->stream) != hipSuccess))
       return gfail(g, EPPK_ERR_DEVICE, std::string(who) + ": upload failed");
     // (random-top-k hashes the request's index in the BATCH: r0 = the shard's first row, so that the split does not show)
-    rc = run_pick(m, (const uint8_t*)m->d_tk_reqs, cnt, cand_mask ? m->d_tk_mask : nullptr, m->d_tk_pick, m->d_tk_score, m->stream, k, random, seed, lo);
+    rc = run_pick(m, (const uint8_t*)m->d_tk_reqs, cnt, cand_mask ? m->d_tk_mask : nullptr, m->d_tk_pick, m->d_tk_score, m->stream, k, random, seed, lo,
+                  nullptr, nullptr, wrand);
     if (rc) return mfail(rc);
     if (hipMemcpyAsync(g->h_tk_pick + (size_t)lo * ok, m->d_tk_pick, (size_t)cnt * ok * 4u, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
         hipMemcpyAsync(g->h_tk_score + (size_t)lo * ok, m->d_tk_score, (size_t)cnt * ok * 8u, hipMemcpyDeviceToHost, m->stream) != hipSuccess)
@@ -3207,6 +3300,11 @@ int eppk_group_pick_topk(eppk_group* g, const void* reqs, uint32_t n_reqs, const
 int eppk_group_pick_random_topk(eppk_group* g, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, uint64_t seed, int32_t* out_pick,
                                 double* out_score) {
   return group_topk(g, "eppk_group_pick_random_topk", reqs, n_reqs, cand_mask, k, true, seed, out_pick, out_score);
+}
+
+int eppk_group_pick_weighted_random(eppk_group* g, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, uint64_t seed,
+                                    int32_t* out_pick, double* out_score) {
+  return group_topk(g, "eppk_group_pick_weighted_random", reqs, n_reqs, cand_mask, k, false, seed, out_pick, out_score, true);
 }
 
 int eppk_group_pick_stage_buffers(eppk_group* g, uint32_t set, void** reqs, uint64_t** cand_mask) {

@@ -3540,6 +3540,303 @@ __global__ __launch_bounds__(512) void pick_generic_kernel(KSnap sn, KIndex ix, 
   }
 }
 
+// ---- WEIGHTED-RANDOM pick kernel (picker "weighted-random", SEMANTICS.md §3c) -------------------------------------------
+// Round i of request r samples one of its remaining candidates C_i with probability w[p] / S, w[p] = the pod's total when that is
+// positive, else 0, through a perfect binary tree of 4096 leaves in which pod p sits at leaf 64*(p mod 64) + p/64: the pods of
+// lane l (64j + l, the lane-word layout of every pick kernel) are the subtree of leaves 64l .. 64l+63, its "column".
+// One wavefront per request, occupancy-sized persistent grid:
+//   pass 1   every lane scores its J pods in chain order (the generic kernel's arithmetic) and folds their weights into its
+//            column's pairwise tree (levels 0..6: blocks of 4 leaves, then a carry of four);
+//   7..12    a butterfly over the lanes (__shfl_xor 1..32); lane l keeps the value of every node above its column (lv[]);
+//   descent  wave-uniform down the lane levels (readlane) to column l*; the wave then scores that column again (lane j: pod
+//            64j + l*), builds its levels 0..6 by the same butterfly -- bit-identical to pass 1: IEEE addition commutes -- and
+//            descends to the leaf;
+//   round i+1  the pick's leaf goes to 0 in that column, its levels and the lane levels are rebuilt: no second pass.
+// When no remaining candidate has a positive total (S == 0) the pick is the (u mod |C_i|)-th candidate in ascending pod order.
+// LDS: lead[J*64] f64 (the chain's leading pod-only scorers under the snapshot-wide QUEUE normalisers, folded in chain order:
+//      what unmasked rows and masked rows with those normalisers start from) | kvs[J*64] f64 clamp01(1 - kv) | queue[J*64] u32 |
+//      per wave pw[pwn] f64 clamp01(cnt/n) | per wave 64 lane words (set_from_list's scratch).
+__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {     // the mixer of random_select_kernel (SEMANTICS.md §3b)
+  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+  z ^= z >> 27; z *= 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+__device__ __forceinline__ double readlane_f64(double v, uint32_t l) {
+  const uint64_t b = __builtin_bit_cast(uint64_t, v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, (int)l);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), (int)l);
+  return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+template <typename LW>
+__device__ __forceinline__ LW readlane_lw(LW v, uint32_t l) {
+  if constexpr (sizeof(LW) == 8) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)l);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), (int)l);
+    return (LW)(((uint64_t)hi << 32) | lo);
+  } else {
+    return (LW)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)l);
+  }
+}
+// Levels 1..6 of a 64-leaf subtree held one leaf per lane: v[m] at lane i = node i >> m of level m.
+__device__ __forceinline__ void wave_tree(double (&v)[7]) {
+#pragma unroll
+  for (int m = 0; m < 6; ++m) v[m + 1] = v[m] + __shfl_xor(v[m], 1 << m);
+}
+// One descent through such a subtree (lanes as leaves): at a node with children A, B go to A if B == 0 or x < A, else x -= A and
+// go to B (SEMANTICS.md §3c step 6).  Returns the leaf's lane.
+__device__ __forceinline__ uint32_t wave_descend(const double (&v)[7], double& x) {
+  uint32_t at = 0;
+#pragma unroll
+  for (int m = 5; m >= 0; --m) {
+    const double a = readlane_f64(v[m], at), b = readlane_f64(v[m], at + (1u << m));
+    if (!(b == 0.0 || x < a)) { x = x - a; at += 1u << m; }
+    at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at);
+  }
+  return at;
+}
+
+template <typename LW, int NPL, bool MASKED>
+__global__ __launch_bounds__(1024) void pick_wrand_kernel(KSnap sn, KIndex ix, KChain ch, const uint8_t* __restrict__ reqs,
+                                                          uint32_t stride, uint32_t n_reqs, uint32_t pwn,
+                                                          const uint64_t* __restrict__ cand_mask,
+                                                          int32_t* __restrict__ out_pick, double* __restrict__ out_score,
+                                                          uint32_t k, uint64_t seed, uint32_t r0) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const uint32_t np = sn.J * 64u;
+  double* s_lead = (double*)smem;
+  double* s_kvs = s_lead + np;
+  uint32_t* s_q = (uint32_t*)(s_kvs + np);
+  const int lane = (int)(threadIdx.x & 63u);
+  const uint32_t wib = threadIdx.x >> 6;
+  const uint32_t wpb = blockDim.x >> 6;
+  double* s_pw = (double*)(s_q + np) + (size_t)wib * pwn;
+  LW* s_scr = (LW*)((double*)(s_q + np) + (size_t)wpb * pwn) + (size_t)wib * 64u;
+
+  bool has_q = false, has_l = false, has_p = false;
+  uint32_t lead = 0;                                   // the chain's leading run of pod-only scorers (QUEUE / KV_CACHE)
+  for (uint32_t i = 0; i < ch.n; ++i) {
+    has_q |= ch.kind[i] == 1u; has_l |= ch.kind[i] == 3u; has_p |= ch.kind[i] == 4u;
+    if (lead == i && (ch.kind[i] == 1u || ch.kind[i] == 2u)) lead = i + 1u;
+  }
+  {
+    const uint32_t qmin = sn.qrange[0], qmax = sn.qrange[1];
+    const double qden = (double)(qmax - qmin);
+    for (uint32_t p = threadIdx.x; p < np; p += blockDim.x) {
+      const uint32_t q = sn.queue[p];
+      const double kvs = clamp01(1.0 - sn.kv[p]);
+      double t = 0.0;
+      for (uint32_t i = 0; i < lead; ++i) {
+        const double s = ch.kind[i] == 1u ? clamp01((qmax == qmin) ? 1.0 : (double)(qmax - q) / qden) : kvs;
+        t = t + s * ch.w[i];
+      }
+      s_lead[p] = t; s_kvs[p] = kvs; s_q[p] = q;
+    }
+  }
+  s_scr[lane] = (LW)0;
+  __syncthreads();
+
+  const LW valid = (LW)(valid_word<LW>(sn.n_pods, lane) & ((const LW*)sn.act_t)[lane]);
+  const uint32_t gwave = blockIdx.x * wpb + wib;
+  const uint32_t nwaves = gridDim.x * wpb;
+  for (uint32_t r = gwave; r < n_reqs; r += nwaves) {
+    const uint8_t* row = reqs + (size_t)r * stride;
+    const int32_t adapter = __builtin_amdgcn_readfirstlane(((const int32_t*)row)[0]);
+    const uint32_t nb = (uint32_t)__builtin_amdgcn_readfirstlane(((const int32_t*)row)[1]);
+    int32_t* opick = out_pick + (size_t)r * k;
+    double* oscore = out_score ? out_score + (size_t)r * k : nullptr;
+    if (__builtin_expect(nb > (stride - 8u) / 8u || adapter < -1 || adapter >= (int32_t)EPPK_MAX_ADAPTERS, 0)) {
+      // out-of-range row on a *_device entry point: not scored (EPPK_NO_PICK), flagged (eppk_launch_status)
+      if (lane == 0) {
+        for (uint32_t i = 0; i < k; ++i) { opick[i] = -1; if (oscore) oscore[i] = 0.0; }
+        atomicOr(sn.status, kStatusBadRow);
+      }
+      continue;
+    }
+
+    LW cand = valid;
+    if (MASKED) cand &= transpose_mask<LW>(cand_mask + (size_t)r * sn.J, sn.J, lane);
+    LW c[NPL];
+#pragma unroll
+    for (int q = 0; q < NPL; ++q) c[q] = 0;
+    if (has_p) {                  // (every PREFIX entry of the chain sees the same counts: one walk)
+      prefix_walk<LW, NPL>(ix, (const uint64_t*)(row + 8), nb, lane, c, s_scr);
+      wave_lds_fence();
+      for (uint32_t cnt = (uint32_t)lane; cnt <= nb; cnt += 64u) s_pw[cnt] = clamp01(nb ? (double)cnt / (double)nb : 0.0);
+      wave_lds_fence();
+    }
+    LW thi = 0, tlo = 0;
+    if (has_l) {
+      const uint32_t arow = adapter >= 0 ? (uint32_t)adapter : 128u;
+      thi = ((const LW*)sn.thi_t)[(size_t)arow * 64u + (uint32_t)lane];
+      tlo = ((const LW*)sn.tlo_t)[(size_t)arow * 64u + (uint32_t)lane];
+    }
+    // QUEUE normalisers over the request's candidates (masked rows), as the generic kernel
+    uint32_t qmin = sn.qrange[0], qmax = sn.qrange[1];
+    if (MASKED && has_q) {
+      uint32_t mn = 0xFFFFFFFFu, mx = 0u;
+      for (uint32_t j = 0; j < sn.J; ++j) {
+        if ((cand >> j) & 1) {
+          const uint32_t q = s_q[j * 64u + (uint32_t)lane];
+          mn = q < mn ? q : mn;
+          mx = q > mx ? q : mx;
+        }
+      }
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) {
+        const uint32_t omn = (uint32_t)__shfl_xor((int)mn, off), omx = (uint32_t)__shfl_xor((int)mx, off);
+        mn = omn < mn ? omn : mn;
+        mx = omx > mx ? omx : mx;
+      }
+      qmin = (uint32_t)__builtin_amdgcn_readfirstlane((int)mn);
+      qmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)mx);
+    }
+    const double qden = (double)(qmax - qmin);
+    const bool lead_ok = qmin == sn.qrange[0] && qmax == sn.qrange[1];    // the staged leading terms hold for this row
+    // the total of pod p (SEMANTICS.md §2 step 2): bits = its tier (bits 0..1) and prefix count (bits 2..)
+    auto total = [&](uint32_t p, uint32_t tier, uint32_t cnt) -> double {
+      double t = 0.0;
+      uint32_t i0 = 0;
+      if (lead_ok) { t = s_lead[p]; i0 = lead; }
+      for (uint32_t i = i0; i < ch.n; ++i) {
+        double s;
+        switch (ch.kind[i]) {
+          case 1u: s = clamp01((qmax == qmin) ? 1.0 : (double)(qmax - s_q[p]) / qden); break;
+          case 2u: s = s_kvs[p]; break;
+          case 3u: s = tier == 3u ? 1.0 : tier == 2u ? 0.8 : tier == 1u ? 0.6 : 0.0; break;
+          default: s = s_pw[cnt]; break;
+        }
+        t = t + s * ch.w[i];
+      }
+      return t;
+    };
+
+    // pass 1: this lane's column, levels 0..6 (blocks of 4 leaves, then a carry of four)
+    double lv[7];
+    {
+      double s2 = 0.0, s3 = 0.0, s4 = 0.0, s5 = 0.0, col = 0.0;
+      for (uint32_t b = 0; b < 16u; ++b) {
+        double n2 = 0.0;
+        if (b * 4u < sn.J) {
+          const uint32_t sh = b * 4u;
+          const uint32_t cb = (uint32_t)(cand >> sh), hb = (uint32_t)(thi >> sh), lb = (uint32_t)(tlo >> sh);
+          uint32_t pb[NPL];
+#pragma unroll
+          for (int q = 0; q < NPL; ++q) pb[q] = (uint32_t)(c[q] >> sh);
+          // scorer-major over the block (chain order within every leaf, so the same sums): the block's LDS reads of one scorer
+          // are in flight together instead of one leaf's round trips after another
+          uint32_t tier[4], cnt[4], p[4];
+          double l[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            p[e] = (sh + (uint32_t)e) * 64u + (uint32_t)lane;
+            if (sh + (uint32_t)e >= sn.J) p[e] = (uint32_t)lane;          // (a leaf past the pods: any pod's reads, weight 0 below)
+            tier[e] = (((hb >> e) & 1u) << 1) | ((lb >> e) & 1u);
+            cnt[e] = 0;
+#pragma unroll
+            for (int q = 0; q < NPL; ++q) cnt[e] |= ((pb[q] >> e) & 1u) << q;
+            l[e] = lead_ok ? s_lead[p[e]] : 0.0;
+          }
+          for (uint32_t i = lead_ok ? lead : 0u; i < ch.n; ++i) {
+            const uint32_t kind = ch.kind[i];
+            const double w = ch.w[i];
+            double sc[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              switch (kind) {
+                case 1u: sc[e] = clamp01((qmax == qmin) ? 1.0 : (double)(qmax - s_q[p[e]]) / qden); break;
+                case 2u: sc[e] = s_kvs[p[e]]; break;
+                case 3u: sc[e] = tier[e] == 3u ? 1.0 : tier[e] == 2u ? 0.8 : tier[e] == 1u ? 0.6 : 0.0; break;
+                default: sc[e] = s_pw[cnt[e]]; break;
+              }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) l[e] = l[e] + sc[e] * w;
+          }
+#pragma unroll
+          for (int e = 0; e < 4; ++e) l[e] = (sh + (uint32_t)e < sn.J && ((cb >> e) & 1u) && l[e] > 0.0) ? l[e] : 0.0;
+          n2 = (l[0] + l[1]) + (l[2] + l[3]);
+        }
+        if (!(b & 1u)) { s2 = n2; continue; }
+        const double n3 = s2 + n2;
+        if (!(b & 2u)) { s3 = n3; continue; }
+        const double n4 = s3 + n3;
+        if (!(b & 4u)) { s4 = n4; continue; }
+        const double n5 = s4 + n4;
+        if (!(b & 8u)) s5 = n5;
+        else col = s5 + n5;
+      }
+      lv[0] = col;
+    }
+    wave_tree(lv);                 // levels 7..12: lv[m] = node (lane >> m) of level 6 + m; lv[6] = S
+
+    uint32_t n_c = (uint32_t)__popcll((unsigned long long)cand);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) n_c += (uint32_t)__shfl_xor((int)n_c, off);
+    n_c = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_c);
+    for (uint32_t i = 0; i < k; ++i) {
+      if (n_c == 0u) {             // C_i empty: this entry and every later one
+        if (lane == 0)
+          for (uint32_t e = i; e < k; ++e) { opick[e] = -1; if (oscore) oscore[e] = 0.0; }
+        break;
+      }
+      const uint64_t u = splitmix64(seed + ((uint64_t)(r0 + r) + 1ull) * 0x9E3779B97F4A7C15ull + (uint64_t)i);
+      const double S = readlane_f64(lv[6], 0u);
+      const bool weighted = S != 0.0;
+      double x = 0.0;
+      uint32_t ls = 0, js = 0;
+      if (weighted) {
+        x = ((double)(u >> 11) * 0x1p-53) * S;
+        ls = wave_descend(lv, x);  // (levels 12 .. 7: lv[m] of lanes at, at + 2^m)
+      } else {                     // the (u mod |C_i|)-th candidate, ascending: pod 64j + l before 64j' + l' iff (j, l) < (j', l')
+        uint32_t rem = (uint32_t)(u % (uint64_t)n_c);
+        for (uint32_t j = 0; j < sn.J; ++j) {
+          uint64_t m = __ballot((int)((cand >> j) & 1));
+          const uint32_t pc = (uint32_t)__popcll(m);
+          if (rem < pc) {
+            for (; rem; --rem) m &= m - 1ull;
+            ls = (uint32_t)__builtin_ctzll(m);
+            js = j;
+            break;
+          }
+          rem -= pc;
+        }
+      }
+      // column ls again, one pod per lane: lane j scores pod 64j + ls
+      double cv[7], tc = 0.0;
+      {
+        const LW cw = readlane_lw<LW>(cand, ls), hw = readlane_lw<LW>(thi, ls), lw = readlane_lw<LW>(tlo, ls);
+        LW cc[NPL];
+#pragma unroll
+        for (int q = 0; q < NPL; ++q) cc[q] = readlane_lw<LW>(c[q], ls);
+        cv[0] = 0.0;
+        const uint32_t j = (uint32_t)lane;
+        if (j < sn.J) {
+          const uint32_t tier = (uint32_t)(((hw >> j) & 1) << 1) | (uint32_t)((lw >> j) & 1);
+          uint32_t cnt = 0;
+#pragma unroll
+          for (int q = 0; q < NPL; ++q) cnt |= (uint32_t)((cc[q] >> j) & 1) << q;
+          tc = total(j * 64u + ls, tier, cnt);
+          cv[0] = (((cw >> j) & 1) && tc > 0.0) ? tc : 0.0;
+        }
+      }
+      wave_tree(cv);               // levels 1..6 of the column: cv[6] == lv[0] of lane ls, bit for bit
+      if (weighted) js = wave_descend(cv, x);
+      if (lane == 0) {
+        opick[i] = (int32_t)(js * 64u + ls);
+        if (oscore) oscore[i] = readlane_f64(tc, js);
+      }
+      if (i + 1u < k) {            // without replacement: the pick's leaf to 0, its column's levels, the levels above
+        if ((uint32_t)lane == ls) cand &= (LW)~((LW)1 << js);
+        --n_c;
+        if ((uint32_t)lane == js) cv[0] = 0.0;
+        wave_tree(cv);
+        if ((uint32_t)lane == ls) lv[0] = cv[6];
+        wave_tree(lv);
+      }
+    }
+  }
+}
+
 // ---- on-device prompt hashing (SEMANTICS.md §4; 0602-…/README.md:99) -------------------------------------
 // One thread per request walks its prompt block by block: h[i] = XXH64(block_i || LE64(h[i-1])), seed 0, and
 // writes the complete request row {adapter, n_blocks, h[0..)}.  Blocks are 8-byte multiples (block_chars % 8

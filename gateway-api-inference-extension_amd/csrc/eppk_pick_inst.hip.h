@@ -10,6 +10,7 @@ struct PickVariant {       // which instantiation a context needs (eppk.hip: pic
   bool masked, topk;       // candidate masks; ordered fallbacks (TOPK instantiation of the fast / generic kernel)
   bool big;                // index of 4 GiB and more
   bool has_l, has_p, p_first, gen;
+  bool wrand;              // picker "weighted-random" (pick_wrand_kernel; `masked` selects its instantiation, the rest is unused)
 };
 
 const void* pick_kernel_u16_6(const PickVariant& v);
@@ -73,6 +74,7 @@ static const void* fast_kernel_ptr(const PickVariant& v) {
 const void* EPPK_PICK_INST_NAME(const PickVariant& v) {
   using LW = EPPK_PICK_INST_LW;
   constexpr int NPL = EPPK_PICK_INST_NPL;
+  if (v.wrand) return v.masked ? (const void*)pick_wrand_kernel<LW, NPL, true> : (const void*)pick_wrand_kernel<LW, NPL, false>;
   if (!v.fast) {
     if (v.topk) return v.masked ? (const void*)pick_generic_kernel<LW, NPL, true, (int)EPPK_MAX_TOPK> : (const void*)pick_generic_kernel<LW, NPL, false, (int)EPPK_MAX_TOPK>;
     return v.masked ? (const void*)pick_generic_kernel<LW, NPL, true, 1> : (const void*)pick_generic_kernel<LW, NPL, false, 1>;

@@ -728,14 +728,15 @@ struct SchedulingResult {  // interface.go:81-84
   std::string primary_profile_name;
 };
 
-enum class PickerKind { BestScore, RandomTopK };   // examples/example.yaml `selection: best-score | random-top-3`
+enum class PickerKind { BestScore, RandomTopK, WeightedRandom };   // examples/example.yaml `selection: best-score | random-top-3`; weighted-random:
+                                                                   // 006-scheduler/README.md:154 (SEMANTICS.md §3c)
 
 struct ProfileSpec {
   std::string name;
   std::function<bool(const Endpoint&)> filter;   // conjunction of the profile's Filter plugins (interface.go:113-118); empty = all
   std::vector<WeightedScorer> scorers;           // interface.go:132-135, order = summation order
   PickerKind picker = PickerKind::BestScore;     // interface.go:137-142
-  uint32_t k = 3;                                // random-top-k
+  uint32_t k = 3;                                // random-top-k (weighted-random draws one endpoint per request)
 };
 
 class ProfileHandler {  // interface.go:91-111
@@ -852,10 +853,13 @@ class Scheduler {  // interface.go:55-66
             std::memcpy(rows + (size_t)i * stride, &hdr, sizeof hdr);
           }
           picks_.resize(m); scores_.resize(m);
-          // the random-top-k rule hashes a request's index in the batch handed to the library: this profile's group, in request order
+          // the random-top-k and weighted-random rules hash a request's index in the batch handed to the library: this profile's group, in
+          // request order
           const int rc = staged ? eppk_pick_batch_staged(p.ctx.get(), m, 0, picks_.data(), scores_.data())
                          : p.spec.picker == PickerKind::BestScore
                              ? eppk_pick_batch(p.ctx.get(), rows, m, nullptr, picks_.data(), scores_.data())
+                         : p.spec.picker == PickerKind::WeightedRandom
+                             ? eppk_pick_weighted_random(p.ctx.get(), rows, m, nullptr, 1, seed + lo, picks_.data(), scores_.data())
                              : eppk_pick_random_topk(p.ctx.get(), rows, m, nullptr, p.spec.k, seed + lo, picks_.data(), scores_.data());
           if (rc != EPPK_OK) return {Code::Internal, eppk_last_error(p.ctx.get())};
           for (uint32_t i = 0; i < m; ++i) {

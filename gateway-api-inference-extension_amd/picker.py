@@ -431,6 +431,31 @@ class BatchedPicker:
                                                     scores.ctypes.data), "pick_random_topk")
         return picks, scores
 
+    def pick_weighted_random(self, reqs: np.ndarray, seed: int, k: int = 1, mask: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """Picker "weighted-random" (SEMANTICS.md §3c): k seeded draws per request without replacement, each candidate with probability
+        proportional to its positive total.  ([R, k] candidate indices, [R, k] totals); column 0 is the pick."""
+        if not 1 <= int(k) <= 8:
+            raise EppkError(-1, "pick_weighted_random: k out of range (1..8)")
+        reqs = np.ascontiguousarray(reqs, dtype=np.uint64)
+        assert reqs.ndim == 2 and reqs.shape[1] == self.row_words, "request row stride mismatch"
+        R = reqs.shape[0]
+        picks = np.full((R, k), -1, dtype=np.int32)
+        scores = np.zeros((R, k), dtype=np.float64)
+        mptr = None
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint64)
+            assert mask.shape == (R, (self.n_pods + 63) // 64), "mask shape mismatch"
+            mptr = mask.ctypes.data
+        self._check(self._lib.eppk_pick_weighted_random(self._ctx, reqs.ctypes.data, R, mptr, int(k), seed & 0xFFFFFFFFFFFFFFFF, picks.ctypes.data,
+                                                        scores.ctypes.data), "pick_weighted_random")
+        return picks, scores
+
+    def pick_weighted_random_device(self, d_reqs: int, n_reqs: int, d_mask: Optional[int], k: int, seed: int, d_pick: int, d_score: Optional[int],
+                                    stream: int = 0) -> None:
+        """eppk_pick_weighted_random_device: n_reqs * k entries at d_pick / d_score, asynchronous on `stream` (0 = the context's)."""
+        self._check(self._lib.eppk_pick_weighted_random_device(self._ctx, d_reqs, n_reqs, d_mask, int(k), seed & 0xFFFFFFFFFFFFFFFF, d_pick, d_score,
+                                                               stream or None), "pick_weighted_random_device")
+
     def set_assumed_load(self, epochs: int) -> None:
         """Assumed load in `epochs` sub-batches per batch (SEMANTICS.md §2b); 0 = off."""
         self._check(self._lib.eppk_set_assumed_load(self._ctx, int(epochs)), "set_assumed_load")
@@ -674,6 +699,16 @@ class DeviceGroup:
         scores = np.empty(R, dtype=np.float64)
         self._check(self._lib.eppk_group_pick_random_topk(self._g, reqs.ctypes.data, R, mptr, k, seed & 0xFFFFFFFFFFFFFFFF, picks.ctypes.data,
                                                           scores.ctypes.data), "group_pick_random_topk")
+        return picks, scores
+
+    def pick_weighted_random(self, reqs: np.ndarray, seed: int, k: int = 1, mask: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """eppk_group_pick_weighted_random: ([R, k] candidate indices, [R, k] totals), column 0 = the pick."""
+        reqs, mask, mptr = self._rows_and_mask(reqs, mask)
+        R = reqs.shape[0]
+        picks = np.full((R, max(int(k), 1)), -1, dtype=np.int32)
+        scores = np.zeros((R, max(int(k), 1)), dtype=np.float64)
+        self._check(self._lib.eppk_group_pick_weighted_random(self._g, reqs.ctypes.data, R, mptr, int(k), seed & 0xFFFFFFFFFFFFFFFF, picks.ctypes.data,
+                                                              scores.ctypes.data), "group_pick_weighted_random")
         return picks, scores
 
     # -- the pipelined host path over the group (eppk_group_pick_stage_*) ---------------------------------------------

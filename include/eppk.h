@@ -359,6 +359,20 @@ int eppk_pick_random_topk(eppk_ctx* ctx, const void* reqs, uint32_t n_reqs, cons
 int eppk_pick_random_topk_device(eppk_ctx* ctx, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, uint32_t k, uint64_t seed,
                                  int32_t* d_out_pick, double* d_out_score, void* stream);
 
+/* Picker "weighted-random" (docs/proposals/006-scheduler/README.md:154: filter, score into a prioritized list, then SAMPLE from it;
+ * SEMANTICS.md §3c): k (1..EPPK_MAX_TOPK) rounds per request without replacement; round i picks a remaining candidate p with
+ * probability t[p] / S (t = the total eppk_pick_batch reports, S = the sum of the positive totals left), drawn with the word
+ * splitmix64(seed + (r+1) * 0x9E3779B97F4A7C15 + i) (round 0's word is random-top-k's) through a fixed binary tree of binary64 sums,
+ * so that a result is reproducible bit for bit.  A request whose remaining candidates have no positive total gets the
+ * (word mod count)-th of them in index order; one with fewer than k candidates is padded with EPPK_NO_PICK / 0.0.
+ * out_pick / out_score (nullable) hold n_reqs * k entries as for eppk_pick_topk; out_pick[r*k] is the request's pick (what the
+ * assumed load of SEMANTICS.md §2b counts).  Errors, row checks and staging as eppk_pick_random_topk.  Cost: one kernel that scores
+ * every (request, pod) pair, 0.69 ms per 64k x 4096 batch on an MI355X against 27.5 us for eppk_pick_topk(k = 4). */
+int eppk_pick_weighted_random(eppk_ctx* ctx, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, uint64_t seed,
+                              int32_t* out_pick, double* out_score);
+int eppk_pick_weighted_random_device(eppk_ctx* ctx, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, uint32_t k,
+                                     uint64_t seed, int32_t* d_out_pick, double* d_out_score, void* stream);
+
 /* Assumed load (docs/proposals/006-scheduler/README.md:154-156; SEMANTICS.md §2b).  epochs = E >= 1: every batch handed to a pick
  * entry point of this context is scored in E epochs of ceil(n_reqs / E) consecutive requests; after each epoch the queue gauge of
  * every picked endpoint grows by one per request routed to it and everything derived from the gauge is rebuilt on the device
@@ -423,6 +437,10 @@ int eppk_group_pick_topk(eppk_group* g, const void* reqs, uint32_t n_reqs, const
                          double* out_score);
 int eppk_group_pick_random_topk(eppk_group* g, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, uint64_t seed,
                                 int32_t* out_pick, double* out_score);
+/* The picker "weighted-random" over the group, sharded the same way: equal to eppk_pick_weighted_random on the unsharded batch, bit
+ * for bit (the rule hashes a request's index in the BATCH). */
+int eppk_group_pick_weighted_random(eppk_group* g, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, uint64_t seed,
+                                    int32_t* out_pick, double* out_score);
 /* The PIPELINED host path over the group: eppk_pick_stage_buffers / _begin / _end (above) with the same calling rules, flags
  * (EPPK_PICK_LEARN) and error behaviour.  A set's rows / masks / results live in ONE pinned buffer of the group that every member's DMA
  * engine reads; member i uploads and scores its shard on its own staging set's stream while the caller fills the other set.  With
