@@ -610,6 +610,8 @@ int launch_wrand(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_
   uint32_t pwn = c->pwn;
   auto lds_of = [&](uint32_t wpb) { return (size_t)sn.J * 64u * 20u + (size_t)wpb * pwn * 8u + (size_t)wpb * 64u * (size_t)c->lw_bytes; };
   uint32_t threads = 1024u;
+  // (for devices with 64 KB of LDS.  With gfx950's 160 KB the branch is never taken: at the API's limits -- 4096 pods, 256 blocks,
+  // u64 lane words -- 16 wavefronts need 81 920 + 16 * (2 064 + 512) = 123 136 bytes, so no test on this device can reach it)
   if (lds_of(threads / 64u) > c->max_lds) threads = 512u;
   const uint32_t wpb = threads / 64u;
   const size_t lds = lds_of(wpb);

@@ -195,6 +195,39 @@ def test_device_entry_point_on_a_stream_with_assumed_load(pkg, orc, ref):
     _same((picks, scores), (wp, ws), "assumed load E = 4, device form")
 
 
+@pytest.mark.parametrize("E", [1, 3, "R"])
+def test_assumed_load_epochs_on_masked_rows_with_a_leading_queue(pkg, orc, ref, E):
+    """Epochs of R, R/3 and one request with candidate masks and k = 2 on a chain that STARTS with QUEUE: between epochs the snapshot's
+    queue gauges, the QUEUE range and with them the staged leading terms are rebuilt, and the word of request r hashes its index in
+    the batch, not in its epoch.  Coarse queue gauges (0..2): one assumed request moves the range.  The numpy side is the loop of
+    test_device_entry_point_on_a_stream_with_assumed_load: bump queue[round 0's pick] after every epoch."""
+    chain = [(Q, 3), (KV, 1), (PF, 2), (Q, -1)]
+    wl = pkg.workload.make_workload(3, R=60, P=300, B=8)
+    R, k, seed = wl.R, 2, 0xF00D0000F00D
+    E = R if E == "R" else E
+    pods = wl.pods.copy()
+    pods["queue"] = np.random.default_rng(5).integers(0, 3, pods.shape[0])
+    mask = _mixed_mask(wl, 321)
+    oix = _oracle_index(orc, wl)
+    with pkg.BatchedPicker(chain, max_pods=300, max_blocks=wl.B, max_batch=R, index_slots=wl.index_slots) as pk:
+        pk.publish(pods)
+        pk.index_insert(wl.index_hashes, wl.index_pods)
+        pk.set_assumed_load(E)
+        got = pk.pick_weighted_random(wl.reqs, seed, k, mask)
+    per = (R + E - 1) // E
+    wp = np.full((R, k), -1, dtype=np.int32)
+    ws = np.zeros((R, k))
+    for lo in range(0, R, per):
+        hi = min(R, lo + per)
+        T = _totals(orc, chain, pods, oix, wl.reqs[lo:hi], mask[lo:hi])
+        wp[lo:hi], ws[lo:hi] = ref.weighted_random(T, k, seed, np.arange(lo, hi))
+        for p in wp[lo:hi, 0]:
+            if p >= 0:
+                pods["queue"][p] += 1
+    _same(got, (wp, ws), f"assumed load E = {E}, masked, k = 2, leading QUEUE")
+    assert np.any(wp[:, 0] < 0) and np.any(wp[:, 1] < 0) and np.any(wp[:, 1] >= 0)     # empty rows, padded rows, full rows
+
+
 def test_errors_and_bad_rows(pkg):
     import torch
     wl = pkg.workload.make_workload(3, R=300, P=500)
