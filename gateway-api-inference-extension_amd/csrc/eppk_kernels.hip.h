@@ -2478,13 +2478,17 @@ __device__ __forceinline__ uint32_t pick_quad_body(const uint32_t vblock, const 
     if (have4) sid_of(std::integral_constant<int, 4>{});
     bool all8 = false;
     uint32_t Wx = 0u;                                                 // hits found further on in a bucket chain (walk below): not in `codes`
-    // Two rare steps, in a loop because either can make the other necessary: (1) a row whose first 20 keys are all hits needs steps 5..7;
-    // (2) a row whose first missing key sits in an overflowed bucket follows the chain -- and may arrive at 20 hits that way.  (Until round 6
-    // step (1) ran once, ahead of (2): a returning request with a displaced key among its first 20, in a wavefront whose other rows
-    // stopped short of 20, was scored with 20 matched blocks instead of 32 -- right pick, low score; found by the `revisit` bench leg.)
+    // Two rare steps, in a loop because either can make the other necessary: (1) a row whose first 17 keys are all hits needs keys 17..31
+    // (step 4 for every quad's own key, steps 5..7); (2) a row whose first missing key sits in an overflowed bucket follows the chain -- and
+    // may arrive at 17 hits that way.  Until keys 17..31 have been fetched, step 4 holds key 16's bucket in EVERY quad: its overflow flag
+    // says nothing about keys 17..19, so the walk of the first pass stops at 17 hits and the second pass fetches and goes on from there.
+    // (History: until round 6 step (1) ran once, ahead of (2): a returning request with a displaced key among its first 20, in a wavefront
+    // whose other rows stopped short of 20, was scored with 20 matched blocks instead of 32 -- found by the `revisit` bench leg.  Until
+    // tests/test_gpu_displaced.py the second pass fetched only for a row with EXACTLY 17 hits while the first pass walked on past 17 on key
+    // 16's flag: keys 16 and 17 both displaced left the row at 18 hits, keys 18..31 never looked at -- right pick, low score.)
 #pragma unroll 1
     for (int pass = 0; pass < 2; ++pass) {
-      const bool more = !all8 && __any(m == kAheadKeys && nbc > kAheadKeys);
+      const bool more = !all8 && __any(m >= kAheadKeys && nbc > m);
       if (pass == 1 && !more) break;
       if (__builtin_expect(more, 0)) {   // keys 17..31 on demand: step 4 once more, for every quad's own key, and steps 5..7
         const uint32_t b1 = home_bucket(cur.h1, ix.shift);
@@ -2520,7 +2524,9 @@ __device__ __forceinline__ uint32_t pick_quad_body(const uint32_t vblock, const 
 #pragma unroll
         for (int i = 0; i < 8; ++i)
           if (i < kAhead || all8) ovf |= (pb.w[i].x & 1u) << i;
-        bool pend = m < nbc && q == (m & 3u) && j == 0u && ((ovf >> (m >> 2)) & 1u);
+        // (before keys 17..31 are in, only keys 0..16 may be walked: step 4's flag is key 16's bucket's)
+        const uint32_t mlim = all8 ? nbc : (nbc < kAheadKeys ? nbc : kAheadKeys);
+        bool pend = m < mlim && q == (m & 3u) && j == 0u && ((ovf >> (m >> 2)) & 1u);
         while (__any(pend)) {
           uint32_t sf = 0u;                                                // 0 = absent, else 0x80000000 | the set id of the key found further on
           if (pend) {
@@ -2538,7 +2544,7 @@ __device__ __forceinline__ uint32_t pick_quad_body(const uint32_t vblock, const 
           Wx |= add;
           W |= add;
           m = (uint32_t)__builtin_ctzll(~(unsigned long long)W);
-          pend = add != 0u && m < nbc && q == (m & 3u) && j == 0u && ((ovf >> (m >> 2)) & 1u);
+          pend = add != 0u && m < mlim && q == (m & 3u) && j == 0u && ((ovf >> (m >> 2)) & 1u);
         }
       }
     }

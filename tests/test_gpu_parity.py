@@ -263,26 +263,32 @@ def test_masked_requests_with_their_own_queue_normalisers_from_the_lists(pkg, or
     assert_same(*run_both(pkg, orc, wl2, chain=chain, mask=mask, max_pods=max_pods))
 
 
-def _home_bucket(h: np.ndarray, n_buckets: int) -> np.ndarray:
-    """Home bucket of a block hash, as libeppk places it (eppk_kernels.hip.h home_bucket): top log2(buckets) bits of
-    (lo ^ hi) * 0x9E3779B1 mod 2^32.  Test-side restatement used only to BUILD colliding keys."""
-    lg = int(n_buckets).bit_length() - 1
-    f = ((h & np.uint64(0xFFFFFFFF)) ^ (h >> np.uint64(32))).astype(np.uint64)
-    return ((f * np.uint64(0x9E3779B1)) & np.uint64(0xFFFFFFFF)) >> np.uint64(32 - lg)
+def _placement():
+    """tests/index_placement.py: the test-side restatement of the index's bucket geometry (protocol v5), loaded by file name."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("index_placement", os.path.join(os.path.dirname(os.path.abspath(__file__)), "index_placement.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
 
 
 @pytest.mark.parametrize("chain", [[(KV, 1), (PF, 5)], [(PF, 5), (Q, 1), (KV, 1)]], ids=["fast", "generic"])
 def test_overflowed_buckets(pkg, orc, chain):
-    """More keys than a 7-key bucket holds hash to the same home bucket: the surplus lives in the following buckets and
-    look-ups (hits and misses) must walk there.  64 slots = 8 buckets, 30 keys, 24 of them with home bucket 1."""
+    """More keys than a 5-key bucket holds hash to the same home bucket: the surplus lives in the following buckets and
+    look-ups (hits and misses) must walk there.  64 slots = 16 buckets, 30 keys, 24 of them with home bucket 1 (they fill buckets 1..5
+    together with the 6 keys of home bucket 3, which the surplus pushes on in turn)."""
     P, B, slots = 200, 8, 64
     rng = np.random.default_rng(11)
-    cand = rng.integers(1, 2**63, 200000, dtype=np.uint64)
-    hb = _home_bucket(cand, slots // 8)
-    hot = cand[hb == 1][:24]
-    cold = cand[hb == 3][:6]
-    absent = cand[hb == 1][24:40]           # never inserted; their home bucket is full and overflowed
+    ipl = _placement()
+    hot_all, cold = ipl.keys_for_buckets([1, 3], [40, 6], slots, seed=11)
+    hot = hot_all[:24]
+    absent = hot_all[24:40]                 # never inserted; their home bucket is full and overflowed
     assert hot.size == 24 and cold.size == 6 and absent.size == 16
+    assert np.all(ipl.home_bucket(hot_all, slots) == 1) and np.all(ipl.home_bucket(cold, slots) == 3)
+    model = ipl.Table(slots)
+    for h in np.concatenate([hot, cold]).tolist():
+        model.insert(h)
+    assert {1, 2, 3, 4, 5} <= model.flags and model.live() == 30      # five buckets full and overflowed, whatever the insert order
     keys = np.concatenate([hot, cold])
     ih = np.repeat(keys, 3)
     ip = (np.arange(ih.size, dtype=np.uint32) * 7) % P
@@ -299,6 +305,7 @@ def test_overflowed_buckets(pkg, orc, chain):
         pk.publish(pods)
         pk.index_insert(ih, ip)
         assert pk.index_size() == keys.size
+        assert pk.index_selfcheck() == 0
         picks, scores = pk.pick(reqs)
     oix = orc.OracleIndex()
     oix.insert(ih, ip)
