@@ -248,6 +248,9 @@ struct eppk_ctx {
   uint32_t fast_threads = 1024;  // workgroup size of the fast kernel (EPPK_FAST_THREADS overrides: tuning knob)
   size_t max_lds = 65536;        // LDS a workgroup may use (160 KB on gfx950)
   int max_wg_per_cu = 0;         // EPPK_MAX_WG_PER_CU: cap on resident workgroups per CU (0 = what the occupancy query allows; tuning knob)
+  int max_cu = 0;                // EPPK_MAX_CU: num_cu is clamped to [1, max_cu] at create, before the resident units' CUs come off (0 = the device's
+                                 // count; tuning and test knob: a narrow grid gives every wavefront of the persistent kernels many loop trips)
+  uint32_t geom[4] = {0, 0, 0, 0};   // eppk_launch_geometry: {quad_grid, quad_threads, grid, threads} of the most recent pick launch (0 = not launched)
 
   std::string err;
 };
@@ -402,6 +405,7 @@ int resident_park(eppk_ctx* c);
 int launch_pick(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_mask, int32_t* d_pick,
                 double* d_score, hipStream_t st, uint32_t topk = 1, uint32_t* d_learn = nullptr, bool* wrote_learn = nullptr) {
   if (wrote_learn) *wrote_learn = false;
+  c->geom[0] = c->geom[1] = c->geom[2] = c->geom[3] = 0u;     // (eppk_launch_geometry: filled in where a kernel is launched)
   const bool masked = d_mask != nullptr;
   // masked batches use the fast kernel's MASKED instantiation, indexes of 4 GiB and more its BIG one
   const bool fast = c->canonical;   // (ordered fallbacks: extra selection rounds of the same kernel; generic TOPK kernel otherwise)
@@ -540,6 +544,7 @@ int launch_pick(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t
       uint32_t* learn_arg = (tail && topk == 1) ? d_learn : nullptr;
       void* qargs[] = {&sn, &ix, &tl, &reqs8, &stride, &n_reqs, &pwn, &d_mask, &d_pick, &d_score, &stats, &d_cnt, &d_list, &defer_cap, &d_total, &d_total_next,
                        &topk, &d_done, &h_rep, &chf, &learn_arg};
+      c->geom[0] = quad_grid; c->geom[1] = c->quad_threads;
       if (tail) {                           // one launch: every workgroup is its own work-list pass
         HIPCHK(c, hipExtLaunchKernel(quad_fn, dim3(quad_grid), dim3(c->quad_threads), qargs, quad_lds, st, e0, e1, 0));
         if (wrote_learn) *wrote_learn = learn_arg != nullptr;
@@ -591,6 +596,7 @@ int launch_pick(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t
     void* args[] = {&sn, &ix, &ch, &reqs8, &stride, &n_reqs, &pwn, &d_mask, &d_pick, &d_score, &stats, &topk};
     HIPCHK(c, hipExtLaunchKernel(fn, dim3(grid), dim3(threads), args, lds, st, e0, e1, 0));
   }
+  c->geom[2] = grid; c->geom[3] = threads;
   c->last_done = e1;
   c->last_stream = st;
   if (prof_now) {
@@ -627,6 +633,7 @@ int launch_wrand(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_
   uint32_t stride = c->stride;
   void* args[] = {&sn, &ix, &ch, &reqs8, &stride, &n_reqs, &pwn, &d_mask, &d_pick, &d_score, &k, &seed, &r0};
   HIPCHK(c, hipExtLaunchKernel(fn, dim3(grid), dim3(threads), args, lds, st, nullptr, nullptr, 0));
+  c->geom[0] = c->geom[1] = 0u; c->geom[2] = grid; c->geom[3] = threads;
   c->last_done = nullptr;
   c->last_stream = st;
   return EPPK_OK;
@@ -1254,6 +1261,10 @@ int eppk_create(const eppk_cfg* cfg, eppk_ctx** out) {
     if (v >= 64 && v <= 1024 && v % 64 == 0) c->fast_threads = (uint32_t)v;
   }
   if (const char* mw = getenv("EPPK_MAX_WG_PER_CU")) c->max_wg_per_cu = atoi(mw) > 0 ? atoi(mw) : 0;
+  if (const char* mc = getenv("EPPK_MAX_CU")) {             // (any value that is set clamps: below 1 means 1)
+    c->max_cu = atoi(mc) > 1 ? atoi(mc) : 1;
+    if (c->num_cu > c->max_cu) c->num_cu = c->max_cu;
+  }
   if (const char* rs = getenv("EPPK_RESIDENT")) c->resident_on = atoi(rs) != 0;
   if (const char* qf = getenv("EPPK_RESIDENT_QUAD_FROM")) c->resident_quad_from = atoi(qf) > 0 ? (uint32_t)atoi(qf) : 1u;
   bool resident_max_set = false;
@@ -2378,6 +2389,7 @@ int launch_pick_cands(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const ui
   (void)by_lane_word(c, [&](auto tag) { using LW = decltype(tag); fn = (const void*)eppk::pick_cands_kernel<LW>; return EPPK_OK; });
   void* args[] = {&sn, &ix, &ch, &reqs8, &stride, &n_reqs, &d_mask, &d_pick, &d_score, &k};
   HIPCHK(c, hipExtLaunchKernel(fn, dim3(grid), dim3(256), args, 0, st, e0, e1, 0));
+  c->geom[0] = c->geom[1] = 0u; c->geom[2] = grid; c->geom[3] = 256u;
   c->last_done = e1;
   c->last_stream = st;
   if (c->prof) c->launches++;
@@ -2783,6 +2795,12 @@ int eppk_resident_stats(const eppk_ctx* c, uint64_t* batches, uint64_t* starts) 
   if (batches) *batches = c->res_batches;
   if (starts) *starts = c->res_starts;
   return c->resident_on ? 1 : 0;
+}
+
+int eppk_launch_geometry(const eppk_ctx* c, uint32_t out[4]) {
+  if (!c || !out) return EPPK_ERR_ARG;
+  for (int i = 0; i < 4; ++i) out[i] = c->geom[i];
+  return EPPK_OK;
 }
 
 int eppk_quad_stats(eppk_ctx* c, uint64_t* launches, uint64_t* deferred) {

@@ -548,6 +548,15 @@ class BatchedPicker:
         self._check(self._lib.eppk_quad_stats(self._ctx, C.byref(a), C.byref(b)), "quad_stats")
         return int(a.value), int(b.value)
 
+    def launch_geometry(self) -> Tuple[int, int, int, int]:
+        """(quad_grid, quad_threads, grid, threads) of the most recent pick launch: workgroups and threads per workgroup of the
+        four-requests-per-wavefront kernel and of the kernel launched behind (or instead of) it; 0 = not launched.  Does not
+        synchronise (include/eppk.h eppk_launch_geometry).  A wavefront of a persistent kernel makes
+        ceil(blocks / (grid * threads / 64)) loop trips."""
+        g = (C.c_uint32 * 4)()
+        self._check(self._lib.eppk_launch_geometry(self._ctx, g), "launch_geometry")
+        return int(g[0]), int(g[1]), int(g[2]), int(g[3])
+
     # -- measurement ------------------------------------------------------------------------
     def profile(self, on) -> None:
         """False / 0: off; True / 1: every pick launch carries events and probe counts; N > 1: every Nth launch (sampled)."""

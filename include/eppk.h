@@ -565,6 +565,14 @@ int eppk_chain_is_fused(const eppk_ctx* ctx);
  * off; EPPK_QUAD_MIN = smallest batch that takes it, default 4096 requests; EPPK_QUAD_TAIL=0 keeps the two-launch form.  A workload
  * that keeps deferring a large part of its batches pauses the route by itself.) */
 int eppk_quad_stats(eppk_ctx* ctx, uint64_t* launches, uint64_t* deferred);
+/* Diagnostic.  The launch geometry of the most recent pick launch of this context: out = {quad_grid, quad_threads, grid, threads} --
+ * workgroups and threads per workgroup of the four-requests-per-wavefront kernel, then of the kernel launched for (or instead of) the
+ * rows it deferred: the general kernel (fused or generic), its work-list form, the weighted-random or the candidates kernel.  A kernel
+ * that was not launched reports 0 (the one-launch form of the quad route has no second launch).  A batch answered by a resident
+ * workgroup launches nothing and leaves the four numbers as they were.  Does not synchronise: the launch path stores the four numbers
+ * in the context.  What a test that narrows the grid (EPPK_MAX_CU, EPPK_MAX_WG_PER_CU, EPPK_QUAD_THREADS, EPPK_FAST_THREADS:
+ * INTEGRATION.md) asserts before it relies on the number of loop trips a wavefront makes: trips = ceil(blocks / (grid * threads / 64)). */
+int eppk_launch_geometry(const eppk_ctx* ctx, uint32_t out[4]);
 
 /* Enabling resets the event ring, the launch counter and the probe statistics.  While enabled,
  * every pick launch (on == 1) -- or every on-th one (on > 1: sampled, what a throughput measurement uses so that the
