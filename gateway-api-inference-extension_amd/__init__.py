@@ -19,4 +19,5 @@ every pick raises.
 """
 from . import _lib, distributed, metrics, picker, workload  # noqa: F401
 from ._lib import EppkError, lib_path, load_library  # noqa: F401
-from .picker import BatchedPicker, DeviceGroup, Endpoint, PickResult, RoundRobinPicker, ScorerKind, Unavailable, subset_mask  # noqa: F401
+from .picker import (VERDICT_BAD_CLASS, VERDICT_SHED, BatchedPicker, DeviceGroup, Endpoint, OnEmpty, PickResult, PredicateKind,  # noqa: F401
+                     RoundRobinPicker, ScorerKind, Unavailable, subset_mask, verdict_stage)

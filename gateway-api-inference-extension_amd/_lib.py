@@ -10,6 +10,8 @@ EPPK_MAX_PODS = 4096
 EPPK_MAX_ADAPTERS = 128
 EPPK_MAX_BLOCKS = 256
 EPPK_NO_PICK = -1
+EPPK_MAX_FILTER_PROGRAMS = 4
+EPPK_MAX_PREDICATES = 4
 
 STATUS = {0: "EPPK_OK", -1: "EPPK_ERR_ARG", -2: "EPPK_ERR_LIMIT", -3: "EPPK_ERR_DEVICE",
           -4: "EPPK_ERR_NO_SNAPSHOT", -5: "EPPK_ERR_INDEX_FULL", -6: "EPPK_ERR_NOMEM"}
@@ -27,6 +29,7 @@ SYMBOLS = [
     "eppk_pick_batch_subset", "eppk_pick_batch_candidates_device",
     "eppk_launch_status", "eppk_pick_random_topk", "eppk_pick_random_topk_device", "eppk_set_assumed_load",
     "eppk_pick_weighted_random", "eppk_pick_weighted_random_device", "eppk_group_pick_weighted_random",
+    "eppk_set_filters", "eppk_filter_masks_device", "eppk_filter_masks", "eppk_pick_filtered_device", "eppk_pick_filtered",
     "eppk_group_create", "eppk_group_destroy", "eppk_group_last_error", "eppk_group_size", "eppk_group_ctx", "eppk_group_ranks_seen",
     "eppk_group_set_min_shard", "eppk_group_snapshot_publish", "eppk_group_index_clear", "eppk_group_index_insert",
     "eppk_group_index_remove_pod", "eppk_group_index_advance_epoch", "eppk_group_index_evict_older", "eppk_group_pick_batch",
@@ -52,6 +55,16 @@ class Cfg(C.Structure):
                 ("max_blocks", C.c_uint32), ("max_batch", C.c_uint32), ("index_slots", C.c_uint32),
                 ("n_scorers", C.c_uint32), ("reserved", C.c_uint32),
                 ("chain", WeightedScorer * EPPK_MAX_SCORERS)]
+
+
+class Predicate(C.Structure):
+    """eppk_predicate: one stage of a filter program (SEMANTICS.md §2c)."""
+    _fields_ = [("kind", C.c_uint32), ("on_empty", C.c_uint32), ("u", C.c_uint32), ("reserved", C.c_uint32), ("f", C.c_double)]
+
+
+class FilterProgram(C.Structure):
+    """eppk_filter_program."""
+    _fields_ = [("n_stages", C.c_uint32), ("reserved", C.c_uint32), ("stage", Predicate * EPPK_MAX_PREDICATES)]
 
 
 def lib_path() -> str:
@@ -127,6 +140,11 @@ def load_library() -> C.CDLL:
     lib.eppk_pick_weighted_random.argtypes = [vp, vp, u32, vp, u32, u64, vp, vp]
     lib.eppk_pick_weighted_random_device.argtypes = [vp, vp, u32, vp, u32, u64, vp, vp, vp]
     lib.eppk_set_assumed_load.argtypes = [vp, u32]
+    lib.eppk_set_filters.argtypes = [vp, C.POINTER(FilterProgram), u32]
+    lib.eppk_filter_masks_device.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]
+    lib.eppk_filter_masks.argtypes = [vp, vp, u32, vp, vp, vp, vp]
+    lib.eppk_pick_filtered_device.argtypes = [vp, vp, u32, vp, vp, u32, vp, vp, vp, vp]
+    lib.eppk_pick_filtered.argtypes = [vp, vp, u32, vp, vp, u32, vp, vp, vp]
     lib.eppk_group_create.argtypes = [C.POINTER(Cfg), C.POINTER(i32), u32, u32, C.POINTER(vp)]
     lib.eppk_group_destroy.argtypes = [vp]
     lib.eppk_group_destroy.restype = None

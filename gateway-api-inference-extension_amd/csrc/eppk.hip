@@ -8,6 +8,7 @@
 #define EPPK_MAIN_UNIT
 #include "eppk_kernels.hip.h"
 #include "eppk_pick_inst.hip.h"
+#include "eppk_filter.hip.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -181,6 +182,15 @@ struct eppk_ctx {
   uint32_t host_flags = 0;        // sticky launch-status flags raised by the host side (EPPK_LAUNCH_LEARN_FAILED)
   void* d_tk_reqs = nullptr; uint64_t* d_tk_mask = nullptr; int32_t* d_tk_pick = nullptr; double* d_tk_score = nullptr;  // eppk_pick_topk
   eppk_pod_row* h_rows = nullptr; eppk_pod_row* d_rows = nullptr;  // raw pod rows of a publish (pinned staging + device copy)
+
+  // metric predicates of the Filter phase (SEMANTICS.md §2c; eppk_filter.hip.h).  The planes are rebuilt in front of a filter launch
+  // whenever the rows or the programs have changed since they were built (filt_gen: advanced by a publish, by eppk_set_filters and by
+  // every assumed-load bump, which edits d_rows in place) or the launch goes to another stream than the build did.
+  eppk::KFilter filt{};
+  uint64_t* d_fplanes = nullptr;
+  uint64_t filt_gen = 1, filt_built = 0; hipStream_t filt_stream = nullptr;
+  uint64_t* d_fmask = nullptr; size_t fmask_rows = 0;       // mask rows of eppk_pick_filtered_device (they never leave the device)
+  uint8_t* d_fcls = nullptr; uint8_t* d_fverdict = nullptr; // host-buffer forms: max_batch bytes each
 
   // measurement
   bool prof = false;
@@ -1042,6 +1052,7 @@ int run_pick(eppk_ctx* c, const uint8_t* d_reqs, uint32_t n_reqs, const uint64_t
     if (E) {    // the assumed load of what this epoch routed, then everything derived from the queue gauge again
       hipLaunchKernelGGL(assumed_bump_kernel, dim3((cnt + 255u) / 256u), dim3(256), 0, st, c->d_rows, (const int32_t*)pick, cnt, ok, c->n_pods);
       HIPCHK(c, hipGetLastError());
+      ++c->filt_gen;            // (the filter planes were built from the rows as they stood before the bump)
       rc = rebuild_snapshot(c, c->n_pods, st);
       if (rc) return rc;
     }
@@ -1473,6 +1484,7 @@ void eppk_destroy(eppk_ctx* c) {
   if (c->check.h_bad) (void)hipHostFree(c->check.h_bad);
   if (c->h_reports) (void)hipHostFree((void*)c->h_reports);
   if (c->h_rows) (void)hipHostFree(c->h_rows);
+  (void)hipFree(c->d_fplanes); (void)hipFree(c->d_fmask); (void)hipFree(c->d_fcls); (void)hipFree(c->d_fverdict);
   (void)hipFree(c->d_rows); (void)hipFree(c->d_rm); (void)hipFree(c->d_rs_pick); (void)hipFree(c->d_rs_score); (void)hipFree(c->d_learn);
   if (c->h_reqs) (void)hipHostFree(c->h_reqs);
   if (c->h_mask) (void)hipHostFree(c->h_mask);
@@ -1515,6 +1527,7 @@ int eppk_snapshot_publish(eppk_ctx* c, const eppk_pod_row* rows, uint32_t n_pods
     std::memcpy(c->h_rows, rows, (size_t)n_pods * sizeof(eppk_pod_row));
     HIPCHK(c, hipMemcpyAsync(c->d_rows, c->h_rows, (size_t)n_pods * sizeof(eppk_pod_row), hipMemcpyHostToDevice, c->stream));
   }
+  ++c->filt_gen;
   int rc = rebuild_snapshot(c, n_pods, c->stream);
   if (rc) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2738,6 +2751,184 @@ int eppk_set_assumed_load(eppk_ctx* c, uint32_t epochs) {
   if (!c) return EPPK_ERR_ARG;
   if (epochs > 65536u) return fail(c, EPPK_ERR_LIMIT, "eppk_set_assumed_load: more than 65536 epochs per batch");
   c->assumed_epochs = epochs;
+  return EPPK_OK;
+}
+
+// ---- metric predicates of the Filter phase (SEMANTICS.md §2c; eppk_filter.hip.h) ------------------------------------------
+
+int eppk_set_filters(eppk_ctx* c, const eppk_filter_program* progs, uint32_t n_programs) {
+  if (!c || (!progs && n_programs)) return fail(c, EPPK_ERR_ARG, "eppk_set_filters: null argument");
+  if (n_programs > EPPK_MAX_FILTER_PROGRAMS)
+    return fail(c, EPPK_ERR_ARG, "eppk_set_filters: " + std::to_string(n_programs) + " programs (at most " + std::to_string(EPPK_MAX_FILTER_PROGRAMS) + ")");
+  eppk::KFilter f{};
+  f.n_programs = n_programs;
+  for (uint32_t g = 0; g < n_programs; ++g) {
+    const eppk_filter_program& pg = progs[g];
+    const std::string where = "eppk_set_filters: program " + std::to_string(g);
+    if (pg.n_stages > EPPK_MAX_PREDICATES)
+      return fail(c, EPPK_ERR_ARG, where + " has " + std::to_string(pg.n_stages) + " stages (at most " + std::to_string(EPPK_MAX_PREDICATES) + ")");
+    if (pg.reserved != 0u) return fail(c, EPPK_ERR_ARG, where + ": reserved field is not zero");
+    f.n_stages[g] = pg.n_stages;
+    for (uint32_t s = 0; s < pg.n_stages; ++s) {
+      const eppk_predicate& pd = pg.stage[s];
+      const std::string at = where + " stage " + std::to_string(s);
+      if (pd.kind < EPPK_PRED_QUEUE_LE || pd.kind > EPPK_PRED_QUEUE_WITHIN) return fail(c, EPPK_ERR_ARG, at + ": unknown predicate kind " + std::to_string(pd.kind));
+      if (pd.on_empty != EPPK_ON_EMPTY_REQUIRE && pd.on_empty != EPPK_ON_EMPTY_PREFER)
+        return fail(c, EPPK_ERR_ARG, at + ": unknown on_empty policy " + std::to_string(pd.on_empty));
+      if (pd.reserved != 0u) return fail(c, EPPK_ERR_ARG, at + ": reserved field is not zero");
+      f.kind[g][s] = pd.kind; f.on_empty[g][s] = pd.on_empty; f.u[g][s] = pd.u; f.f[g][s] = pd.f;
+      if (pd.kind == EPPK_PRED_LORA_LOADED) f.uses_lora |= 1u;
+      if (pd.kind == EPPK_PRED_LORA_SERVABLE) f.uses_lora |= 2u;
+      if (pd.kind == EPPK_PRED_QUEUE_WITHIN) f.uses_within = 1u;
+    }
+  }
+  c->filt = f;
+  ++c->filt_gen;
+  return EPPK_OK;
+}
+
+namespace {
+// The planes as of the current rows and programs, on `st` in front of the filter launch that reads them (see eppk_ctx::filt_gen).
+int filter_planes(eppk_ctx* c, hipStream_t st) {
+  if (!c->d_fplanes) {
+    HIPCHK(c, hipMalloc((void**)&c->d_fplanes, eppk::kFilterBufBytes));
+    HIPCHK(c, hipMemsetAsync(c->d_fplanes, 0, eppk::kFilterBufBytes, st));      // (on the stream of the build behind it: the context's stream does not wait for the null stream)
+    c->filt_built = 0;
+  }
+  if (c->filt_built == c->filt_gen && c->filt_stream == st) return EPPK_OK;
+  hipLaunchKernelGGL(eppk::filter_planes_kernel, dim3(eppk::kFilterPlaneWords), dim3(64), 0, st, (const eppk_pod_row*)c->d_rows, c->n_pods, c->filt,
+                     c->d_fplanes);
+  HIPCHK(c, hipGetLastError());
+  c->filt_built = c->filt_gen; c->filt_stream = st;
+  return EPPK_OK;
+}
+
+int filter_cls_check(eppk_ctx* c, const char* who, const uint8_t* cls, uint32_t n_reqs) {
+  if (!cls || c->filt.n_programs == 0u) return EPPK_OK;
+  for (uint32_t r = 0; r < n_reqs; ++r)
+    if (cls[r] >= c->filt.n_programs)
+      return fail(c, EPPK_ERR_ARG, std::string(who) + ": request row " + std::to_string(r) + " names class " + std::to_string(cls[r]) + " of " +
+                                       std::to_string(c->filt.n_programs) + " programs");
+  return EPPK_OK;
+}
+
+int filter_host_buffers(eppk_ctx* c) {
+  const size_t mb = c->cfg.max_batch ? c->cfg.max_batch : 1u;
+  if (!c->d_fcls) HIPCHK(c, hipMalloc((void**)&c->d_fcls, mb));
+  if (!c->d_fverdict) HIPCHK(c, hipMalloc((void**)&c->d_fverdict, mb));
+  return EPPK_OK;
+}
+}  // namespace
+
+int eppk_filter_masks_device(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint8_t* d_cls, const uint64_t* d_mask_in, uint64_t* d_mask_out,
+                             uint8_t* d_verdict, void* stream) {
+  if (!c || ((!d_reqs || !d_mask_out) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_filter_masks_device: null argument");
+  if (!c->have_snapshot) return fail(c, EPPK_ERR_NO_SNAPSHOT, "eppk_filter_masks_device: no snapshot published");
+  if (n_reqs == 0) return EPPK_OK;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  int rc = filter_planes(c, st);
+  if (rc) return rc;
+  uint32_t grid = (n_reqs + 3u) / 4u;
+  const uint32_t cap = (uint32_t)c->num_cu * 8u;
+  if (grid > cap) grid = cap;
+  hipLaunchKernelGGL(eppk::filter_masks_kernel, dim3(grid), dim3(256), c->filt.uses_within ? eppk::kFilterQueueLds : 0u, st, (const uint8_t*)d_reqs, c->stride,
+                     n_reqs, d_cls, d_mask_in, d_mask_out, d_verdict, c->n_pods, (const uint64_t*)c->d_fplanes, c->filt, c->d_status);
+  HIPCHK(c, hipGetLastError());
+  return EPPK_OK;
+}
+
+int eppk_filter_masks(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint8_t* cls, const uint64_t* mask_in, uint64_t* out_mask,
+                      uint8_t* out_verdict) {
+  if (!c || ((!reqs || !out_mask) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_filter_masks: null argument");
+  if (!c->have_snapshot) return fail(c, EPPK_ERR_NO_SNAPSHOT, "eppk_filter_masks: no snapshot published");
+  if (n_reqs > c->cfg.max_batch) return fail(c, EPPK_ERR_LIMIT, "eppk_filter_masks: n_reqs > max_batch");
+  if (n_reqs == 0) return EPPK_OK;
+  int rc = validate_rows(c, "eppk_filter_masks", reqs, n_reqs);
+  if (rc) return rc;
+  rc = filter_cls_check(c, "eppk_filter_masks", cls, n_reqs);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  rc = topk_ensure(c, true);
+  if (rc) return rc;
+  rc = filter_host_buffers(c);
+  if (rc) return rc;
+  const size_t J = (c->n_pods + 63u) / 64u;
+  HIPCHK(c, hipMemcpyAsync(c->d_tk_reqs, reqs, (size_t)n_reqs * c->stride, hipMemcpyHostToDevice, c->stream));
+  if (mask_in && J) HIPCHK(c, hipMemcpyAsync(c->d_tk_mask, mask_in, (size_t)n_reqs * J * 8u, hipMemcpyHostToDevice, c->stream));
+  if (cls) HIPCHK(c, hipMemcpyAsync(c->d_fcls, cls, n_reqs, hipMemcpyHostToDevice, c->stream));
+  rc = eppk_filter_masks_device(c, c->d_tk_reqs, n_reqs, cls ? c->d_fcls : nullptr, mask_in && J ? c->d_tk_mask : nullptr, c->d_tk_mask, c->d_fverdict, c->stream);
+  if (rc) return rc;
+  if (J) HIPCHK(c, hipMemcpyAsync(out_mask, c->d_tk_mask, (size_t)n_reqs * J * 8u, hipMemcpyDeviceToHost, c->stream));
+  if (out_verdict) HIPCHK(c, hipMemcpyAsync(out_verdict, c->d_fverdict, n_reqs, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return EPPK_OK;
+}
+
+int eppk_pick_filtered_device(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint8_t* d_cls, const uint64_t* d_cand_mask, uint32_t k,
+                              int32_t* d_out_pick, double* d_out_score, uint8_t* d_out_verdict, void* stream) {
+  if (!c || ((!d_reqs || !d_out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_filtered_device: null argument");
+  if (k < 1 || k > EPPK_MAX_TOPK) return fail(c, EPPK_ERR_ARG, "eppk_pick_filtered_device: k out of range (1..8)");
+  if (!c->have_snapshot) return fail(c, EPPK_ERR_NO_SNAPSHOT, "eppk_pick_filtered_device: no snapshot published");
+  if (n_reqs == 0) return EPPK_OK;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  if (c->filt.n_programs == 0u) {                 // no programs: eppk_pick_topk_device, as it is (an unmasked batch keeps its unmasked route)
+    if (d_out_verdict) HIPCHK(c, hipMemsetAsync(d_out_verdict, 0, n_reqs, st));
+    return eppk_pick_topk_device(c, d_reqs, n_reqs, d_cand_mask, k, d_out_pick, d_out_score, stream);
+  }
+  if (n_reqs > c->fmask_rows) {                   // (rare: the first call, or a larger batch than ever before)
+    { const int rcs = device_sync(c); if (rcs) return rcs; }
+    (void)hipFree(c->d_fmask); c->d_fmask = nullptr; c->fmask_rows = 0;
+    const size_t rows = n_reqs > c->cfg.max_batch ? n_reqs : c->cfg.max_batch;
+    HIPCHK(c, hipMalloc((void**)&c->d_fmask, rows * (c->jmax ? c->jmax : 1u) * 8u));
+    c->fmask_rows = rows;
+  }
+  int rc = eppk_filter_masks_device(c, d_reqs, n_reqs, d_cls, d_cand_mask, c->d_fmask, d_out_verdict, stream);
+  if (rc) return rc;
+  // (a snapshot without pods has no mask words: the caller's own mask pointer, which the pick treats as it always has)
+  return eppk_pick_topk_device(c, d_reqs, n_reqs, c->n_pods ? c->d_fmask : d_cand_mask, k, d_out_pick, d_out_score, stream);
+}
+
+int eppk_pick_filtered(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint8_t* cls, const uint64_t* cand_mask, uint32_t k, int32_t* out_pick,
+                       double* out_score, uint8_t* out_verdict) {
+  if (!c || ((!reqs || !out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_filtered: null argument");
+  if (k < 1 || k > EPPK_MAX_TOPK) return fail(c, EPPK_ERR_ARG, "eppk_pick_filtered: k out of range (1..8)");
+  if (!c->have_snapshot) return fail(c, EPPK_ERR_NO_SNAPSHOT, "eppk_pick_filtered: no snapshot published");
+  if (n_reqs > c->cfg.max_batch) return fail(c, EPPK_ERR_LIMIT, "eppk_pick_filtered: n_reqs > max_batch");
+  if (n_reqs == 0) return EPPK_OK;
+  if (c->filt.n_programs == 0u) {
+    const int rct = eppk_pick_topk(c, reqs, n_reqs, cand_mask, k, out_pick, out_score);
+    if (rct == EPPK_OK && out_verdict) std::memset(out_verdict, 0, n_reqs);
+    return rct;
+  }
+  int rc = validate_rows(c, "eppk_pick_filtered", reqs, n_reqs);
+  if (rc) return rc;
+  rc = filter_cls_check(c, "eppk_pick_filtered", cls, n_reqs);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  rc = topk_ensure(c, true);
+  if (rc) return rc;
+  rc = filter_host_buffers(c);
+  if (rc) return rc;
+  const size_t J = (c->n_pods + 63u) / 64u;
+  if (!J) {                                        // a snapshot without pods: nobody to pick, nothing for a predicate to reject
+    for (size_t i = 0; i < (size_t)n_reqs * k; ++i) { out_pick[i] = EPPK_NO_PICK; if (out_score) out_score[i] = 0.0; }
+    if (out_verdict) std::memset(out_verdict, 0, n_reqs);
+    return EPPK_OK;
+  }
+  HIPCHK(c, hipMemcpyAsync(c->d_tk_reqs, reqs, (size_t)n_reqs * c->stride, hipMemcpyHostToDevice, c->stream));
+  if (cand_mask && J) HIPCHK(c, hipMemcpyAsync(c->d_tk_mask, cand_mask, (size_t)n_reqs * J * 8u, hipMemcpyHostToDevice, c->stream));
+  if (cls) HIPCHK(c, hipMemcpyAsync(c->d_fcls, cls, n_reqs, hipMemcpyHostToDevice, c->stream));
+  rc = eppk_filter_masks_device(c, c->d_tk_reqs, n_reqs, cls ? c->d_fcls : nullptr, cand_mask && J ? c->d_tk_mask : nullptr, c->d_tk_mask, c->d_fverdict,
+                                c->stream);
+  if (rc) return rc;
+  rc = run_pick(c, (const uint8_t*)c->d_tk_reqs, n_reqs, c->d_tk_mask, c->d_tk_pick, c->d_tk_score, c->stream, k, false, 0ull, 0u);
+  if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(out_pick, c->d_tk_pick, (size_t)n_reqs * k * 4u, hipMemcpyDeviceToHost, c->stream));
+  if (out_score) HIPCHK(c, hipMemcpyAsync(out_score, c->d_tk_score, (size_t)n_reqs * k * 8u, hipMemcpyDeviceToHost, c->stream));
+  if (out_verdict) HIPCHK(c, hipMemcpyAsync(out_verdict, c->d_fverdict, n_reqs, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return EPPK_OK;
 }
 

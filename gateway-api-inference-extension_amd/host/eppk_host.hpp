@@ -737,6 +737,8 @@ struct ProfileSpec {
   std::vector<WeightedScorer> scorers;           // interface.go:132-135, order = summation order
   PickerKind picker = PickerKind::BestScore;     // interface.go:137-142
   uint32_t k = 3;                                // random-top-k (weighted-random draws one endpoint per request)
+  std::vector<eppk_predicate> predicates;        // metric predicates behind `filter` (SEMANTICS.md §2c): ONE program, evaluated on the device
+                                                 // against the gauges of the snapshot; empty = none.  A request they shed gets Unavailable.
 };
 
 class ProfileHandler {  // interface.go:91-111
@@ -787,7 +789,15 @@ class Scheduler {  // interface.go:55-66
       eppk_cfg cfg = MakeCfg(sp, go, opt.index_slots, opt.device);
       eppk_ctx* c = nullptr;
       if (eppk_create(&cfg, &c) != EPPK_OK) return {Code::Internal, std::string("profile ") + ps.name + ": " + eppk_last_error(nullptr)};
-      profiles_.push_back(Prof{ps, std::shared_ptr<eppk_ctx>(c, eppk_destroy)});
+      std::shared_ptr<eppk_ctx> ctx(c, eppk_destroy);
+      if (!ps.predicates.empty()) {
+        eppk_filter_program prog;
+        std::memset(&prog, 0, sizeof prog);
+        prog.n_stages = (uint32_t)ps.predicates.size();                 // (more than EPPK_MAX_PREDICATES: the library refuses, naming the program)
+        for (size_t s = 0; s < ps.predicates.size() && s < EPPK_MAX_PREDICATES; ++s) prog.stage[s] = ps.predicates[s];
+        if (eppk_set_filters(c, &prog, 1) != EPPK_OK) return {Code::Internal, std::string("profile ") + ps.name + ": " + eppk_last_error(c)};
+      }
+      profiles_.push_back(Prof{ps, ctx});
       names_.push_back(ps.name);
     }
     return {};
@@ -836,7 +846,8 @@ class Scheduler {  // interface.go:55-66
           // between here and the DMA); the other pickers take a plain buffer
           uint8_t* rows = nullptr;
           bool staged = false;
-          if (p.spec.picker == PickerKind::BestScore) {
+          const bool filtered = !p.spec.predicates.empty();
+          if (p.spec.picker == PickerKind::BestScore && !filtered) {
             void* st = nullptr;
             staged = eppk_host_staging(p.ctx.get(), &st, nullptr) == EPPK_OK && st != nullptr;
             if (staged) { rows = (uint8_t*)st; std::memset(rows, 0, (size_t)m * stride); }
@@ -855,12 +866,24 @@ class Scheduler {  // interface.go:55-66
           picks_.resize(m); scores_.resize(m);
           // the random-top-k and weighted-random rules hash a request's index in the batch handed to the library: this profile's group, in
           // request order
+          // A profile with metric predicates: best-score filters and picks in one call (the mask rows stay on the device); the sampling
+          // pickers take the mask rows the filter leaves (eppk_filter_masks) as their candidate masks.  A shed request has no candidates.
+          const uint64_t* fmask = nullptr;
+          if (filtered && p.spec.picker != PickerKind::BestScore) {
+            uint32_t np = 0;
+            if (eppk_snapshot_info(p.ctx.get(), &np, nullptr) != EPPK_OK) return {Code::Internal, "profile " + p.spec.name + ": no snapshot published"};
+            fmask_.assign((size_t)m * ((np + 63u) / 64u) + 1u, 0ull);
+            if (eppk_filter_masks(p.ctx.get(), rows, m, nullptr, nullptr, fmask_.data(), nullptr) != EPPK_OK) return {Code::Internal, eppk_last_error(p.ctx.get())};
+            fmask = fmask_.data();
+          }
           const int rc = staged ? eppk_pick_batch_staged(p.ctx.get(), m, 0, picks_.data(), scores_.data())
+                         : filtered && p.spec.picker == PickerKind::BestScore
+                             ? eppk_pick_filtered(p.ctx.get(), rows, m, nullptr, nullptr, 1, picks_.data(), scores_.data(), nullptr)
                          : p.spec.picker == PickerKind::BestScore
                              ? eppk_pick_batch(p.ctx.get(), rows, m, nullptr, picks_.data(), scores_.data())
                          : p.spec.picker == PickerKind::WeightedRandom
-                             ? eppk_pick_weighted_random(p.ctx.get(), rows, m, nullptr, 1, seed + lo, picks_.data(), scores_.data())
-                             : eppk_pick_random_topk(p.ctx.get(), rows, m, nullptr, p.spec.k, seed + lo, picks_.data(), scores_.data());
+                             ? eppk_pick_weighted_random(p.ctx.get(), rows, m, fmask, 1, seed + lo, picks_.data(), scores_.data())
+                             : eppk_pick_random_topk(p.ctx.get(), rows, m, fmask, p.spec.k, seed + lo, picks_.data(), scores_.data());
           if (rc != EPPK_OK) return {Code::Internal, eppk_last_error(p.ctx.get())};
           for (uint32_t i = 0; i < m; ++i) {
             auto& res = results[idx[lo + i]][p.spec.name];     // (present even when empty: the profile has run)
@@ -894,6 +917,7 @@ class Scheduler {  // interface.go:55-66
   std::vector<uint8_t> rows_;
   std::vector<int32_t> picks_;
   std::vector<double> scores_;
+  std::vector<uint64_t> fmask_;
 };
 
 }  // namespace eppk_host

@@ -37,6 +37,33 @@ class ScorerKind(enum.IntEnum):
     PREFIX = 4
 
 
+class PredicateKind(enum.IntEnum):
+    """eppk_predicate_kind: the metric predicates of the Filter phase (SEMANTICS.md §2c)."""
+    QUEUE_LE = 1
+    RUNNING_LE = 2
+    KV_LE = 3
+    LORA_LOADED = 4
+    LORA_SERVABLE = 5
+    QUEUE_WITHIN = 6
+
+
+class OnEmpty(enum.IntEnum):
+    """eppk_on_empty: what a stage does when no candidate passes it."""
+    REQUIRE = 0
+    PREFER = 1
+
+
+VERDICT_SHED = 0x40          # EPPK_VERDICT_SHED: a REQUIRE stage emptied the set
+VERDICT_BAD_CLASS = 0x80     # EPPK_VERDICT_BAD_CLASS: cls[r] names no program (device forms)
+
+
+def verdict_stage(s: int) -> int:
+    """EPPK_VERDICT_STAGE(s): the verdict bit of stage s (0..3) -- no candidate passed it."""
+    if not 0 <= int(s) < _lib.EPPK_MAX_PREDICATES:
+        raise ValueError("stage out of range (0..3)")
+    return 1 << int(s)
+
+
 class Unavailable(RuntimeError):
     """codes.Unavailable: no endpoints available (server.go:91-93, request.go:100-102)."""
 
@@ -455,6 +482,75 @@ class BatchedPicker:
         """eppk_pick_weighted_random_device: n_reqs * k entries at d_pick / d_score, asynchronous on `stream` (0 = the context's)."""
         self._check(self._lib.eppk_pick_weighted_random_device(self._ctx, d_reqs, n_reqs, d_mask, int(k), seed & 0xFFFFFFFFFFFFFFFF, d_pick, d_score,
                                                                stream or None), "pick_weighted_random_device")
+
+    # -- metric predicates of the Filter phase (SEMANTICS.md §2c) ----------------------------------
+    def set_filters(self, programs: Sequence[Sequence[Tuple]]) -> None:
+        """programs: up to 4 lists of up to 4 stages (kind, on_empty, threshold); the threshold is the u32 `u` of the integer kinds and
+        the binary64 `f` of KV_LE (the LoRA kinds take none: 0).  A stage may also be an _lib.Predicate.  [] = no programs (the default)."""
+        n = len(programs)
+        arr = (_lib.FilterProgram * max(n, 1))()
+        for g, stages in enumerate(programs):
+            if g >= _lib.EPPK_MAX_FILTER_PROGRAMS:
+                break                                   # (the library refuses the count)
+            stages = list(stages)
+            arr[g].n_stages = len(stages)
+            for s, st in enumerate(stages[:_lib.EPPK_MAX_PREDICATES]):
+                if isinstance(st, _lib.Predicate):
+                    arr[g].stage[s] = st
+                    continue
+                kind, on_empty = int(st[0]), int(st[1])
+                thr = st[2] if len(st) > 2 else 0
+                arr[g].stage[s].kind, arr[g].stage[s].on_empty = kind, on_empty
+                if kind == PredicateKind.KV_LE:
+                    arr[g].stage[s].f = float(thr)
+                else:
+                    arr[g].stage[s].u = int(thr)
+        self._check(self._lib.eppk_set_filters(self._ctx, arr, n), "set_filters")
+
+    def _filter_args(self, reqs, cls, mask):
+        reqs = np.ascontiguousarray(reqs, dtype=np.uint64)
+        assert reqs.ndim == 2 and reqs.shape[1] == self.row_words, "request row stride mismatch"
+        R = reqs.shape[0]
+        if cls is not None:
+            cls = np.ascontiguousarray(cls, dtype=np.uint8)
+            assert cls.shape == (R,), "one class byte per request"
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint64)
+            assert mask.shape == (R, (self.n_pods + 63) // 64), "mask shape mismatch"
+        return reqs, R, cls, mask
+
+    def filter_masks(self, reqs: np.ndarray, cls: Optional[np.ndarray] = None, mask: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """([R, ceil(P/64)] u64 candidate rows, [R] u8 verdicts) of the context's filter programs (include/eppk.h eppk_filter_masks)."""
+        reqs, R, cls, mask = self._filter_args(reqs, cls, mask)
+        out = np.zeros((R, (self.n_pods + 63) // 64), dtype=np.uint64)
+        verdict = np.zeros(R, dtype=np.uint8)
+        self._check(self._lib.eppk_filter_masks(self._ctx, reqs.ctypes.data, R, cls.ctypes.data if cls is not None else None,
+                                                mask.ctypes.data if mask is not None else None, out.ctypes.data, verdict.ctypes.data), "filter_masks")
+        return out, verdict
+
+    def pick_filtered(self, reqs: np.ndarray, k: int = 1, cls: Optional[np.ndarray] = None,
+                      mask: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Filter, then ordered fallbacks over what is left: ([R, k] picks, [R, k] totals, [R] u8 verdicts) (eppk_pick_filtered)."""
+        reqs, R, cls, mask = self._filter_args(reqs, cls, mask)
+        picks = np.full((R, max(int(k), 1)), -1, dtype=np.int32)
+        scores = np.zeros((R, max(int(k), 1)), dtype=np.float64)
+        verdict = np.zeros(R, dtype=np.uint8)
+        self._check(self._lib.eppk_pick_filtered(self._ctx, reqs.ctypes.data, R, cls.ctypes.data if cls is not None else None,
+                                                 mask.ctypes.data if mask is not None else None, int(k), picks.ctypes.data, scores.ctypes.data,
+                                                 verdict.ctypes.data), "pick_filtered")
+        return picks, scores, verdict
+
+    def filter_masks_device(self, d_reqs: int, n_reqs: int, d_cls: Optional[int], d_mask_in: Optional[int], d_mask_out: int,
+                            d_verdict: Optional[int], stream: int = 0) -> None:
+        """eppk_filter_masks_device: device pointers as ints, asynchronous on `stream` (0 = the context's)."""
+        self._check(self._lib.eppk_filter_masks_device(self._ctx, d_reqs, n_reqs, d_cls or None, d_mask_in or None, d_mask_out, d_verdict or None,
+                                                       stream or None), "filter_masks_device")
+
+    def pick_filtered_device(self, d_reqs: int, n_reqs: int, d_cls: Optional[int], d_mask: Optional[int], k: int, d_pick: int,
+                             d_score: Optional[int], d_verdict: Optional[int], stream: int = 0) -> None:
+        """eppk_pick_filtered_device: n_reqs * k entries at d_pick / d_score, asynchronous on `stream` (0 = the context's)."""
+        self._check(self._lib.eppk_pick_filtered_device(self._ctx, d_reqs, n_reqs, d_cls or None, d_mask or None, int(k), d_pick, d_score or None,
+                                                        d_verdict or None, stream or None), "pick_filtered_device")
 
     def set_assumed_load(self, epochs: int) -> None:
         """Assumed load in `epochs` sub-batches per batch (SEMANTICS.md §2b); 0 = off."""

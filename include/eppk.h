@@ -392,6 +392,67 @@ int eppk_pick_weighted_random_device(eppk_ctx* ctx, const void* d_reqs, uint32_t
  * device groups do not support it (every member would bump only its own shard). */
 int eppk_set_assumed_load(eppk_ctx* ctx, uint32_t epochs);
 
+/* ---- metric predicates of the Filter phase (SEMANTICS.md §2c) -------------------------------------------------------------
+ * "A series of predicates that filter candidate endpoints, removing impossible matches" (docs/proposals/006-scheduler/README.md:154;
+ * Filter* of 0845-…/README.md:68-85), evaluated on the device against the gauges of the snapshot: a pod with a full KV cache or a long
+ * queue, or one that cannot serve the request's adapter, stops being a candidate before the scorers run.
+ *
+ * A context holds up to EPPK_MAX_FILTER_PROGRAMS programs of up to EPPK_MAX_PREDICATES stages each; request r runs program cls[r]
+ * (no class array: program 0) -- a shim maps a criticality band to a class byte.  Stage s keeps the candidates that
+ * pass its predicate; when NONE passes, verdict bit s is set and the stage's on_empty policy decides: EPPK_ON_EMPTY_REQUIRE sheds the
+ * request (no candidates, EPPK_VERDICT_SHED), EPPK_ON_EMPTY_PREFER waives the stage (the candidates stay as they were).  A request
+ * that arrives at a stage without candidates passes through untouched, so verdict 0 with no candidates means the subset mask or the
+ * holes left none.  cls[r] >= n_programs: no candidates, EPPK_VERDICT_BAD_CLASS.  With no programs set (the default) the filter is
+ * the identity -- candidate mask minus holes minus bits >= n_pods, verdict 0 -- and the class array is not looked at.
+ * Gauges are read as they stand when the filter launch runs: the rows of the latest publish plus the assumed-load bumps they have
+ * taken (eppk_set_assumed_load); within ONE pick call with assumed-load epochs the candidate sets are not re-evaluated. */
+#define EPPK_MAX_FILTER_PROGRAMS 4u
+#define EPPK_MAX_PREDICATES      4u
+typedef enum eppk_predicate_kind {
+  EPPK_PRED_QUEUE_LE      = 1, /* queue[p] <= u */
+  EPPK_PRED_RUNNING_LE    = 2, /* running[p] <= u */
+  EPPK_PRED_KV_LE         = 3, /* kv_util[p] <= f: raw IEEE compare, no clamp; a NaN gauge or threshold passes nothing */
+  EPPK_PRED_LORA_LOADED   = 4, /* base-model request, or the adapter is in active[p] or waiting[p] */
+  EPPK_PRED_LORA_SERVABLE = 5, /* ... or |active[p]| + |waiting[p]| < max_lora[p]: the pod has a free slot */
+  EPPK_PRED_QUEUE_WITHIN  = 6  /* queue[p] - (min queue over the candidates this stage finds) <= u; never empties a set */
+} eppk_predicate_kind;
+typedef enum eppk_on_empty {
+  EPPK_ON_EMPTY_REQUIRE = 0,   /* no candidate passes: the request is shed */
+  EPPK_ON_EMPTY_PREFER  = 1    /* no candidate passes: the stage is waived */
+} eppk_on_empty;
+#define EPPK_VERDICT_STAGE(s)  (1u << (s))  /* stage s (0..3) found no candidate that passes */
+#define EPPK_VERDICT_SHED      0x40u        /* a REQUIRE stage emptied the set: the predicates shed the request */
+#define EPPK_VERDICT_BAD_CLASS 0x80u        /* cls[r] >= n_programs (device forms; the host-buffer forms refuse the call) */
+typedef struct eppk_predicate { uint32_t kind, on_empty, u, reserved; double f; } eppk_predicate;   /* 24 bytes */
+typedef struct eppk_filter_program { uint32_t n_stages, reserved; eppk_predicate stage[EPPK_MAX_PREDICATES]; } eppk_filter_program;
+
+/* Replace the context's programs (n_programs = 0: none, the default).  EPPK_ERR_ARG, naming the program and the stage, for an unknown
+ * kind or on_empty, a non-zero reserved field, n_stages > EPPK_MAX_PREDICATES or n_programs > EPPK_MAX_FILTER_PROGRAMS; the programs
+ * in force stay as they were.  Takes effect for every later filter launch; synchronous with respect to the host only. */
+int eppk_set_filters(eppk_ctx* ctx, const eppk_filter_program* progs, uint32_t n_programs);
+/* Mask rows of a batch, built on the device: d_mask_out [n_reqs][ceil(n_pods/64)] u64 in the layout of every picker's cand_mask.
+ * d_reqs as for eppk_pick_batch_device (read for the adapter only); d_cls (u8 [n_reqs]), d_mask_in (same layout as the output; bits
+ * >= n_pods are ignored; may be d_mask_out itself) and d_verdict (u8 [n_reqs]) are nullable.  Asynchronous on `stream` (NULL = the
+ * context's).  Stream ordering as for eppk_subset_masks_device: the launch reads the raw rows of the latest publish, so a *_device
+ * call on the caller's own stream must be ordered against publishes (and against assumed-load picks on other streams) by the caller.
+ * ONE stream at a time per context for the filter entry points (this one and eppk_pick_filtered_device), as for assumed load: the
+ * planes the launch reads, and the mask rows of eppk_pick_filtered_device, are one buffer each per context, rebuilt on the stream of
+ * the call that needs them -- a caller that moves to another stream orders it behind the filter launches of the previous one.
+ * A row whose adapter is out of range gets no candidates and raises EPPK_LAUNCH_BAD_REQUEST_ROW. */
+int eppk_filter_masks_device(eppk_ctx* ctx, const void* d_reqs, uint32_t n_reqs, const uint8_t* d_cls, const uint64_t* d_mask_in,
+                             uint64_t* d_mask_out, uint8_t* d_verdict, void* stream);
+/* Host buffers in and out (n_reqs <= max_batch; rows checked as by eppk_pick_batch).  A cls[r] >= n_programs fails the call with
+ * EPPK_ERR_ARG naming the lowest such row; nothing is delivered. */
+int eppk_filter_masks(eppk_ctx* ctx, const void* reqs, uint32_t n_reqs, const uint8_t* cls, const uint64_t* mask_in, uint64_t* out_mask,
+                      uint8_t* out_verdict);
+/* Filter, then the ordered fallbacks of eppk_pick_topk (1 <= k <= EPPK_MAX_TOPK) over what the filter left: the mask rows never leave
+ * the device.  A shed request gets EPPK_NO_PICK / 0.0 like any request without candidates; d_out_verdict (nullable) says why.  Always
+ * the launched route (also under EPPK_RESIDENT=1).  The other pickers compose through eppk_filter_masks_device and their d_cand_mask. */
+int eppk_pick_filtered_device(eppk_ctx* ctx, const void* d_reqs, uint32_t n_reqs, const uint8_t* d_cls, const uint64_t* d_cand_mask,
+                              uint32_t k, int32_t* d_out_pick, double* d_out_score, uint8_t* d_out_verdict, void* stream);
+int eppk_pick_filtered(eppk_ctx* ctx, const void* reqs, uint32_t n_reqs, const uint8_t* cls, const uint64_t* cand_mask, uint32_t k,
+                       int32_t* out_pick, double* out_score, uint8_t* out_verdict);
+
 /* ---- device groups: one picker over several GPUs (SURVEY.md §8(b) "device list", §8(e)) ------------------------------ */
 
 /* A group replicates the snapshot and the prefix index on every member device and shards each batch BY REQUEST: member g scores
