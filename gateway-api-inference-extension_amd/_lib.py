@@ -12,6 +12,9 @@ EPPK_MAX_BLOCKS = 256
 EPPK_NO_PICK = -1
 EPPK_MAX_FILTER_PROGRAMS = 4
 EPPK_MAX_PREDICATES = 4
+EPPK_MAX_TOPK = 8
+EPPK_BOUNDED_SHED, EPPK_BOUNDED_SPILL = 0, 1
+EPPK_RANK_OVERFLOW, EPPK_RANK_NONE = 0x40, 0x80
 
 STATUS = {0: "EPPK_OK", -1: "EPPK_ERR_ARG", -2: "EPPK_ERR_LIMIT", -3: "EPPK_ERR_DEVICE",
           -4: "EPPK_ERR_NO_SNAPSHOT", -5: "EPPK_ERR_INDEX_FULL", -6: "EPPK_ERR_NOMEM"}
@@ -30,6 +33,7 @@ SYMBOLS = [
     "eppk_launch_status", "eppk_pick_random_topk", "eppk_pick_random_topk_device", "eppk_set_assumed_load",
     "eppk_pick_weighted_random", "eppk_pick_weighted_random_device", "eppk_group_pick_weighted_random",
     "eppk_set_filters", "eppk_filter_masks_device", "eppk_filter_masks", "eppk_pick_filtered_device", "eppk_pick_filtered",
+    "eppk_bounded_resolve_device", "eppk_pick_bounded_device", "eppk_pick_bounded", "eppk_group_pick_bounded", "eppk_bounded_geometry",
     "eppk_group_create", "eppk_group_destroy", "eppk_group_last_error", "eppk_group_size", "eppk_group_ctx", "eppk_group_ranks_seen",
     "eppk_group_set_min_shard", "eppk_group_snapshot_publish", "eppk_group_index_clear", "eppk_group_index_insert",
     "eppk_group_index_remove_pod", "eppk_group_index_advance_epoch", "eppk_group_index_evict_older", "eppk_group_pick_batch",
@@ -145,6 +149,11 @@ def load_library() -> C.CDLL:
     lib.eppk_filter_masks.argtypes = [vp, vp, u32, vp, vp, vp, vp]
     lib.eppk_pick_filtered_device.argtypes = [vp, vp, u32, vp, vp, u32, vp, vp, vp, vp]
     lib.eppk_pick_filtered.argtypes = [vp, vp, u32, vp, vp, u32, vp, vp, vp]
+    lib.eppk_bounded_resolve_device.argtypes = [vp, vp, vp, u32, u32, vp, u32, u32, vp, vp, vp, vp, vp]
+    lib.eppk_pick_bounded_device.argtypes = [vp, vp, u32, vp, u32, vp, u32, u32, vp, vp, vp, vp, vp]
+    lib.eppk_pick_bounded.argtypes = [vp, vp, u32, vp, u32, vp, u32, u32, vp, vp, vp, vp]
+    lib.eppk_group_pick_bounded.argtypes = [vp, vp, u32, vp, u32, vp, u32, u32, vp, vp, vp, vp]
+    lib.eppk_bounded_geometry.argtypes = [vp, C.POINTER(u32)]
     lib.eppk_group_create.argtypes = [C.POINTER(Cfg), C.POINTER(i32), u32, u32, C.POINTER(vp)]
     lib.eppk_group_destroy.argtypes = [vp]
     lib.eppk_group_destroy.restype = None

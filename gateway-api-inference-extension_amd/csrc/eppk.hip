@@ -9,6 +9,7 @@
 #include "eppk_kernels.hip.h"
 #include "eppk_pick_inst.hip.h"
 #include "eppk_filter.hip.h"
+#include "eppk_bounded.hip.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -20,6 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <dlfcn.h>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -191,6 +193,14 @@ struct eppk_ctx {
   uint64_t filt_gen = 1, filt_built = 0; hipStream_t filt_stream = nullptr;
   uint64_t* d_fmask = nullptr; size_t fmask_rows = 0;       // mask rows of eppk_pick_filtered_device (they never leave the device)
   uint8_t* d_fcls = nullptr; uint8_t* d_fverdict = nullptr; // host-buffer forms: max_batch bytes each
+
+  // picker "best-score under per-pod caps" (SEMANTICS.md §3d; eppk_bounded.hip.h).  Scratch of the resolve, grown on demand:
+  uint32_t bound_chunk = eppk::kBoundDefaultChunk;          // rows per chunk (EPPK_BOUND_CHUNK: a power of two >= 64)
+  uint32_t* d_bd_hist = nullptr; size_t bd_hist_words = 0;  // [chunks][n_pods] bids of a round per chunk, then their exclusive prefix
+  uint8_t* d_bd_state = nullptr; size_t bd_state_rows = 0;  // a byte per request when the caller takes no ranks
+  uint32_t* d_bd_pods = nullptr;                            // [4][EPPK_MAX_PODS]: room, load (no d_load), and the host forms' cap and load
+  int32_t* d_bd_list = nullptr; double* d_bd_lscore = nullptr; size_t bd_list_rows = 0;   // lists of eppk_pick_bounded_device (x EPPK_MAX_TOPK)
+  int32_t* d_bd_opick = nullptr; double* d_bd_oscore = nullptr; uint8_t* d_bd_orank = nullptr; size_t bd_out_rows = 0;   // results of the host forms
 
   // measurement
   bool prof = false;
@@ -1288,6 +1298,10 @@ int eppk_create(const eppk_cfg* cfg, eppk_ctx** out) {
   if (const char* qp = getenv("EPPK_QUAD_PAUSE")) c->quad_pause_on = atoi(qp) != 0;
   if (const char* zc = getenv("EPPK_ZERO_COPY_MAX")) c->zero_copy_max = atoi(zc) > 0 ? (uint32_t)atoi(zc) : 0u;
   if (const char* hc = getenv("EPPK_HOST_CHECK_MAX")) c->host_check_max = atoi(hc) > 0 ? (uint32_t)atoi(hc) : 0u;
+  if (const char* bc = getenv("EPPK_BOUND_CHUNK")) {        // (anything but a power of two in [64, 2^20] leaves the default)
+    const long v = atol(bc);
+    if (v >= 64 && v <= (1l << 20) && (v & (v - 1)) == 0) c->bound_chunk = (uint32_t)v;
+  }
   if (const char* qt = getenv("EPPK_QUAD_THREADS")) {
     const int v = atoi(qt);
     if (v >= 64 && v <= EPPK_QUAD_MAX_THREADS && v % 64 == 0) c->quad_threads = (uint32_t)v;
@@ -1485,6 +1499,8 @@ void eppk_destroy(eppk_ctx* c) {
   if (c->h_reports) (void)hipHostFree((void*)c->h_reports);
   if (c->h_rows) (void)hipHostFree(c->h_rows);
   (void)hipFree(c->d_fplanes); (void)hipFree(c->d_fmask); (void)hipFree(c->d_fcls); (void)hipFree(c->d_fverdict);
+  (void)hipFree(c->d_bd_hist); (void)hipFree(c->d_bd_state); (void)hipFree(c->d_bd_pods); (void)hipFree(c->d_bd_list); (void)hipFree(c->d_bd_lscore);
+  (void)hipFree(c->d_bd_opick); (void)hipFree(c->d_bd_oscore); (void)hipFree(c->d_bd_orank);
   (void)hipFree(c->d_rows); (void)hipFree(c->d_rm); (void)hipFree(c->d_rs_pick); (void)hipFree(c->d_rs_score); (void)hipFree(c->d_learn);
   if (c->h_reqs) (void)hipHostFree(c->h_reqs);
   if (c->h_mask) (void)hipHostFree(c->h_mask);
@@ -2932,6 +2948,177 @@ int eppk_pick_filtered(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uin
   return EPPK_OK;
 }
 
+// ---- picker "best-score under per-pod caps" (SEMANTICS.md §3d; eppk_bounded.hip.h) -----------------------------------------
+
+namespace {
+
+// Scratch buffers of the bounded picker that share one capacity (`*have`, in units) and have to hold `need` units: kept when they do,
+// else replaced together (rare: the first call, or a larger batch than ever before; what is queued may still read the old ones, so the
+// device is drained first -- include/eppk.h says so).
+struct BoundBuf { void** p; size_t unit_bytes; };
+int bounded_grow(eppk_ctx* c, size_t* have, size_t need, std::initializer_list<BoundBuf> bufs) {
+  if (need <= *have && *have) return EPPK_OK;
+  { const int rcs = device_sync(c); if (rcs) return rcs; }
+  *have = 0;
+  for (const BoundBuf& b : bufs) { (void)hipFree(*b.p); *b.p = nullptr; }
+  for (const BoundBuf& b : bufs)
+    if (hipMalloc(b.p, (need ? need : 1u) * b.unit_bytes) != hipSuccess) {
+      (void)hipGetLastError(); *b.p = nullptr;
+      for (const BoundBuf& f : bufs) { (void)hipFree(*f.p); *f.p = nullptr; }
+      return fail(c, EPPK_ERR_NOMEM, "bounded picker: scratch of " + std::to_string(need * b.unit_bytes) + " bytes");
+    }
+  *have = need ? need : 1u;
+  return EPPK_OK;
+}
+// rows of a per-request buffer: the context's max_batch, or the batch when a *_device caller hands over more
+size_t bounded_rows(const eppk_ctx* c, uint32_t n_reqs) { return n_reqs > c->cfg.max_batch ? (size_t)n_reqs : (size_t)c->cfg.max_batch; }
+
+int bounded_pod_scratch(eppk_ctx* c) {
+  if (!c->d_bd_pods) HIPCHK(c, hipMalloc((void**)&c->d_bd_pods, 4u * EPPK_MAX_PODS * sizeof(uint32_t)));
+  return EPPK_OK;
+}
+
+int bounded_check(eppk_ctx* c, const char* who, uint32_t k, uint32_t policy) {
+  if (k < 1 || k > EPPK_MAX_TOPK) return fail(c, EPPK_ERR_ARG, std::string(who) + ": k out of range (1..8)");
+  if (policy != EPPK_BOUNDED_SHED && policy != EPPK_BOUNDED_SPILL) return fail(c, EPPK_ERR_ARG, std::string(who) + ": unknown policy " + std::to_string(policy));
+  if (!c->have_snapshot) return fail(c, EPPK_ERR_NO_SNAPSHOT, std::string(who) + ": no snapshot published");
+  if (c->assumed_epochs)
+    return fail(c, EPPK_ERR_ARG, std::string(who) + ": assumed load is on (eppk_set_assumed_load); both count load and they do not combine");
+  return EPPK_OK;
+}
+
+// The launches of the resolve on `st` (arguments checked by the caller; n_reqs != 0).
+int bounded_resolve(eppk_ctx* c, const int32_t* d_lists, const double* d_scores, uint32_t n_reqs, uint32_t k, const uint32_t* d_cap, uint32_t cap_all,
+                    uint32_t policy, uint32_t* d_load, int32_t* d_out_pick, double* d_out_score, uint8_t* d_out_rank, hipStream_t st) {
+  const uint32_t P = c->n_pods, chunk = c->bound_chunk;
+  uint8_t* state = d_out_rank;
+  if (!state) {
+    const int rc = bounded_grow(c, &c->bd_state_rows, bounded_rows(c, n_reqs), {{(void**)&c->d_bd_state, 1u}});
+    if (rc) return rc;
+    state = c->d_bd_state;
+  }
+  if (n_reqs <= chunk) {
+    hipLaunchKernelGGL(eppk::bounded_resolve_one_kernel, dim3(1), dim3(eppk::kBoundThreads), 0, st, d_lists, d_scores, n_reqs, k, P, d_cap, cap_all, policy,
+                       d_load, d_out_pick, d_out_score, state, c->d_status);
+    HIPCHK(c, hipGetLastError());
+    return EPPK_OK;
+  }
+  const uint32_t n_chunks = (uint32_t)(((uint64_t)n_reqs + chunk - 1u) / chunk);
+  int rc = bounded_pod_scratch(c);
+  if (rc) return rc;
+  if ((rc = bounded_grow(c, &c->bd_hist_words, (size_t)n_chunks * P, {{(void**)&c->d_bd_hist, sizeof(uint32_t)}}))) return rc;
+  uint32_t* room = c->d_bd_pods;
+  uint32_t* load = d_load;
+  if (!load) {
+    load = c->d_bd_pods + EPPK_MAX_PODS;
+    HIPCHK(c, hipMemsetAsync(load, 0, (size_t)EPPK_MAX_PODS * sizeof(uint32_t), st));
+  }
+  HIPCHK(c, hipMemsetAsync(state, (int)eppk::kBoundUnassigned, n_reqs, st));
+  // grid-stride loops as wide as the CUs this context may use (EPPK_MAX_CU): the results do not depend on the width
+  const uint32_t wide = (uint32_t)c->num_cu * 4u;
+  const uint32_t chunk_grid = n_chunks < wide ? n_chunks : wide;
+  const uint32_t pod_wgs = (P + eppk::kBoundScanPods - 1u) / eppk::kBoundScanPods, pod_grid = pod_wgs < wide ? pod_wgs : wide;
+  const uint32_t row_wgs = (uint32_t)(((uint64_t)n_reqs + eppk::kBoundThreads - 1u) / eppk::kBoundThreads), row_grid = row_wgs < wide * 2u ? row_wgs : wide * 2u;
+  if (P) for (uint32_t j = 0; j < k; ++j) {
+    hipLaunchKernelGGL(eppk::bounded_count_kernel, dim3(chunk_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, n_reqs, k, j, P, chunk, n_chunks,
+                       (const uint8_t*)state, c->d_bd_hist);
+    hipLaunchKernelGGL(eppk::bounded_scan_kernel, dim3(pod_grid), dim3(eppk::kBoundScanSegs * eppk::kBoundScanPods), 0, st, c->d_bd_hist, n_chunks, P, d_cap, cap_all, load, room);
+    hipLaunchKernelGGL(eppk::bounded_assign_kernel, dim3(chunk_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, d_scores, n_reqs, k, j, P, chunk, n_chunks,
+                       (const uint32_t*)c->d_bd_hist, (const uint32_t*)room, state, d_out_pick, d_out_score);
+  }
+  hipLaunchKernelGGL(eppk::bounded_finish_kernel, dim3(row_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, d_scores, n_reqs, k, P, policy, load, state,
+                     d_out_pick, d_out_score, c->d_status);
+  HIPCHK(c, hipGetLastError());
+  return EPPK_OK;
+}
+
+// Host buffers around the resolve: cap and load up, the resolve over device lists on the context's stream, results (and load) down.
+int bounded_host_finish(eppk_ctx* c, const int32_t* d_lists, const double* d_scores, uint32_t n_reqs, uint32_t k, const uint32_t* cap, uint32_t cap_all,
+                        uint32_t policy, uint32_t* load, int32_t* out_pick, double* out_score, uint8_t* out_rank) {
+  int rc = bounded_pod_scratch(c);
+  if (rc) return rc;
+  if ((rc = bounded_grow(c, &c->bd_out_rows, bounded_rows(c, n_reqs),
+                         {{(void**)&c->d_bd_opick, 4u}, {(void**)&c->d_bd_oscore, 8u}, {(void**)&c->d_bd_orank, 1u}}))) return rc;
+  uint32_t* d_cap = c->d_bd_pods + 2u * EPPK_MAX_PODS;
+  uint32_t* d_load = c->d_bd_pods + 3u * EPPK_MAX_PODS;
+  const size_t pod_bytes = (size_t)c->n_pods * sizeof(uint32_t);
+  if (cap && pod_bytes) HIPCHK(c, hipMemcpyAsync(d_cap, cap, pod_bytes, hipMemcpyHostToDevice, c->stream));
+  if (load && pod_bytes) HIPCHK(c, hipMemcpyAsync(d_load, load, pod_bytes, hipMemcpyHostToDevice, c->stream));
+  rc = bounded_resolve(c, d_lists, d_scores, n_reqs, k, cap ? d_cap : nullptr, cap_all, policy, load ? d_load : nullptr, c->d_bd_opick,
+                       out_score ? c->d_bd_oscore : nullptr, c->d_bd_orank, c->stream);
+  if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(out_pick, c->d_bd_opick, (size_t)n_reqs * 4u, hipMemcpyDeviceToHost, c->stream));
+  if (out_score) HIPCHK(c, hipMemcpyAsync(out_score, c->d_bd_oscore, (size_t)n_reqs * 8u, hipMemcpyDeviceToHost, c->stream));
+  if (out_rank) HIPCHK(c, hipMemcpyAsync(out_rank, c->d_bd_orank, n_reqs, hipMemcpyDeviceToHost, c->stream));
+  if (load && pod_bytes) HIPCHK(c, hipMemcpyAsync(load, d_load, pod_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return EPPK_OK;
+}
+
+int bounded_lists(eppk_ctx* c, uint32_t n_reqs) {
+  return bounded_grow(c, &c->bd_list_rows, bounded_rows(c, n_reqs),
+                      {{(void**)&c->d_bd_list, EPPK_MAX_TOPK * 4u}, {(void**)&c->d_bd_lscore, EPPK_MAX_TOPK * 8u}});
+}
+
+}  // namespace
+
+int eppk_bounded_resolve_device(eppk_ctx* c, const int32_t* d_lists, const double* d_list_scores, uint32_t n_reqs, uint32_t k, const uint32_t* d_cap,
+                                uint32_t cap_all, uint32_t policy, uint32_t* d_load, int32_t* d_out_pick, double* d_out_score, uint8_t* d_out_rank,
+                                void* stream) {
+  if (!c || ((!d_lists || !d_out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_bounded_resolve_device: null argument");
+  const int rcc = bounded_check(c, "eppk_bounded_resolve_device", k, policy);
+  if (rcc) return rcc;
+  if (n_reqs == 0) return EPPK_OK;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  return bounded_resolve(c, d_lists, d_list_scores, n_reqs, k, d_cap, cap_all, policy, d_load, d_out_pick, d_out_score, d_out_rank,
+                         stream ? (hipStream_t)stream : c->stream);
+}
+
+int eppk_pick_bounded_device(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, uint32_t k, const uint32_t* d_cap,
+                             uint32_t cap_all, uint32_t policy, uint32_t* d_load, int32_t* d_out_pick, double* d_out_score, uint8_t* d_out_rank,
+                             void* stream) {
+  if (!c || ((!d_reqs || !d_out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_bounded_device: null argument");
+  int rc = bounded_check(c, "eppk_pick_bounded_device", k, policy);
+  if (rc) return rc;
+  if (n_reqs == 0) return EPPK_OK;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if ((rc = bounded_lists(c, n_reqs))) return rc;
+  if ((rc = eppk_pick_topk_device(c, d_reqs, n_reqs, d_cand_mask, k, c->d_bd_list, c->d_bd_lscore, stream))) return rc;
+  return bounded_resolve(c, c->d_bd_list, c->d_bd_lscore, n_reqs, k, d_cap, cap_all, policy, d_load, d_out_pick, d_out_score, d_out_rank,
+                         stream ? (hipStream_t)stream : c->stream);
+}
+
+int eppk_pick_bounded(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint32_t* cap, uint32_t cap_all,
+                      uint32_t policy, uint32_t* load, int32_t* out_pick, double* out_score, uint8_t* out_rank) {
+  if (!c || ((!reqs || !out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_bounded: null argument");
+  int rc = bounded_check(c, "eppk_pick_bounded", k, policy);
+  if (rc) return rc;
+  if (n_reqs > c->cfg.max_batch) return fail(c, EPPK_ERR_LIMIT, "eppk_pick_bounded: n_reqs > max_batch");
+  if (n_reqs == 0) return EPPK_OK;
+  if ((rc = validate_rows(c, "eppk_pick_bounded", reqs, n_reqs))) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const size_t J = (c->n_pods + 63u) / 64u;
+  const bool masked = cand_mask != nullptr && J != 0u;
+  if ((rc = topk_ensure(c, masked))) return rc;
+  if (cand_mask && !J) {                           // a snapshot without pods: nobody to pick (eppk_pick_topk's rule), every list is empty
+    HIPCHK(c, hipMemsetAsync(c->d_tk_pick, 0xFF, (size_t)n_reqs * k * 4u, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_tk_score, 0, (size_t)n_reqs * k * 8u, c->stream));
+  } else {
+    HIPCHK(c, hipMemcpyAsync(c->d_tk_reqs, reqs, (size_t)n_reqs * c->stride, hipMemcpyHostToDevice, c->stream));
+    if (masked) HIPCHK(c, hipMemcpyAsync(c->d_tk_mask, cand_mask, (size_t)n_reqs * J * 8u, hipMemcpyHostToDevice, c->stream));
+    if ((rc = run_pick(c, (const uint8_t*)c->d_tk_reqs, n_reqs, masked ? c->d_tk_mask : nullptr, c->d_tk_pick, c->d_tk_score, c->stream, k, false, 0ull, 0u)))
+      return rc;
+  }
+  return bounded_host_finish(c, c->d_tk_pick, c->d_tk_score, n_reqs, k, cap, cap_all, policy, load, out_pick, out_score, out_rank);
+}
+
+int eppk_bounded_geometry(const eppk_ctx* c, uint32_t out[2]) {
+  if (!c || !out) return EPPK_ERR_ARG;
+  out[0] = c->bound_chunk;
+  out[1] = c->bound_chunk;
+  return EPPK_OK;
+}
+
 // ---- on-device prompt hashing ------------------------------------------------------------------------
 
 int eppk_hash_prompts_device(eppk_ctx* c, const void* d_prompts, uint64_t prompt_stride, const uint32_t* d_prompt_len,
@@ -3552,6 +3739,27 @@ int eppk_group_pick_random_topk(eppk_group* g, const void* reqs, uint32_t n_reqs
 int eppk_group_pick_weighted_random(eppk_group* g, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, uint64_t seed,
                                     int32_t* out_pick, double* out_score) {
   return group_topk(g, "eppk_group_pick_weighted_random", reqs, n_reqs, cand_mask, k, false, seed, out_pick, out_score, true);
+}
+
+int eppk_group_pick_bounded(eppk_group* g, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint32_t* cap, uint32_t cap_all,
+                            uint32_t policy, uint32_t* load, int32_t* out_pick, double* out_score, uint8_t* out_rank) {
+  if (!g || ((!reqs || !out_pick) && n_reqs)) return gfail(g, EPPK_ERR_ARG, "eppk_group_pick_bounded: null argument");
+  eppk_ctx* c0 = g->ctx[0];
+  int rc = bounded_check(c0, "eppk_group_pick_bounded", k, policy);
+  if (rc) return gfail(g, rc, eppk_last_error(c0));
+  // the lists of the whole batch on the host (every member scores its shard), then ONE resolve: caps are global, not per shard
+  std::vector<int32_t> lists((size_t)n_reqs * k);
+  std::vector<double> totals((size_t)n_reqs * k);
+  if ((rc = group_topk(g, "eppk_group_pick_bounded", reqs, n_reqs, cand_mask, k, false, 0ull, lists.data(), totals.data()))) return rc;
+  if (n_reqs == 0) return EPPK_OK;
+  auto mfail = [&](int code) { return gfail(g, code, "device " + std::to_string(g->dev[0]) + ": " + eppk_last_error(c0)); };
+  if (hipSetDevice(g->dev[0]) != hipSuccess) return gfail(g, EPPK_ERR_DEVICE, "eppk_group_pick_bounded: hipSetDevice failed");
+  if ((rc = bounded_lists(c0, n_reqs))) return mfail(rc);
+  if (hipMemcpyAsync(c0->d_bd_list, lists.data(), lists.size() * 4u, hipMemcpyHostToDevice, c0->stream) != hipSuccess ||
+      hipMemcpyAsync(c0->d_bd_lscore, totals.data(), totals.size() * 8u, hipMemcpyHostToDevice, c0->stream) != hipSuccess)
+    return gfail(g, EPPK_ERR_DEVICE, "eppk_group_pick_bounded: upload failed");
+  if ((rc = bounded_host_finish(c0, c0->d_bd_list, c0->d_bd_lscore, n_reqs, k, cap, cap_all, policy, load, out_pick, out_score, out_rank))) return mfail(rc);
+  return EPPK_OK;
 }
 
 int eppk_group_pick_stage_buffers(eppk_group* g, uint32_t set, void** reqs, uint64_t** cand_mask) {

@@ -728,15 +728,20 @@ struct SchedulingResult {  // interface.go:81-84
   std::string primary_profile_name;
 };
 
-enum class PickerKind { BestScore, RandomTopK, WeightedRandom };   // examples/example.yaml `selection: best-score | random-top-3`; weighted-random:
-                                                                   // 006-scheduler/README.md:154 (SEMANTICS.md §3c)
+enum class PickerKind { BestScore, RandomTopK, WeightedRandom, Bounded };   // examples/example.yaml `selection: best-score | random-top-3`;
+                                                                   // weighted-random: 006-scheduler/README.md:154 (SEMANTICS.md §3c); bounded:
+                                                                   // best-score under per-pod caps, 006-scheduler/README.md:140 (SEMANTICS.md §3d)
 
 struct ProfileSpec {
   std::string name;
   std::function<bool(const Endpoint&)> filter;   // conjunction of the profile's Filter plugins (interface.go:113-118); empty = all
   std::vector<WeightedScorer> scorers;           // interface.go:132-135, order = summation order
   PickerKind picker = PickerKind::BestScore;     // interface.go:137-142
-  uint32_t k = 3;                                // random-top-k (weighted-random draws one endpoint per request)
+  uint32_t k = 3;                                // random-top-k; bounded: entries of the fallback list a request may fall through
+                                                 // (weighted-random draws one endpoint per request)
+  uint32_t cap_all = 0;                          // bounded: requests of ONE batch handed to the library any endpoint takes at most; MUST be set
+                                                 // (Configure refuses 0)
+  uint32_t bounded_policy = EPPK_BOUNDED_SHED;   // bounded: what becomes of a request that finds every entry full (SHED: Unavailable)
   std::vector<eppk_predicate> predicates;        // metric predicates behind `filter` (SEMANTICS.md §2c): ONE program, evaluated on the device
                                                  // against the gauges of the snapshot; empty = none.  A request they shed gets Unavailable.
 };
@@ -786,6 +791,8 @@ class Scheduler {  // interface.go:55-66
     for (const ProfileSpec& ps : profiles) {
       SchedulerProfile sp; sp.scorers = ps.scorers;
       GpuPickerOptions go; go.max_pods = opt.max_pods; go.max_blocks = opt.max_blocks; go.max_batch = opt.max_batch;
+      // (a cap of 0 leaves no room on any endpoint: every request would end as Unavailable -- a profile that forgot to set it)
+      if (ps.picker == PickerKind::Bounded && ps.cap_all == 0) return {Code::Internal, std::string("profile ") + ps.name + ": the bounded picker needs cap_all > 0"};
       eppk_cfg cfg = MakeCfg(sp, go, opt.index_slots, opt.device);
       eppk_ctx* c = nullptr;
       if (eppk_create(&cfg, &c) != EPPK_OK) return {Code::Internal, std::string("profile ") + ps.name + ": " + eppk_last_error(nullptr)};
@@ -867,7 +874,8 @@ class Scheduler {  // interface.go:55-66
           // the random-top-k and weighted-random rules hash a request's index in the batch handed to the library: this profile's group, in
           // request order
           // A profile with metric predicates: best-score filters and picks in one call (the mask rows stay on the device); the sampling
-          // pickers take the mask rows the filter leaves (eppk_filter_masks) as their candidate masks.  A shed request has no candidates.
+          // and the bounded pickers take the mask rows the filter leaves (eppk_filter_masks) as their candidate masks.  A shed request has
+          // no candidates; a request the bounded picker sheds for overflow has no endpoint either: both end as Unavailable.
           const uint64_t* fmask = nullptr;
           if (filtered && p.spec.picker != PickerKind::BestScore) {
             uint32_t np = 0;
@@ -881,6 +889,9 @@ class Scheduler {  // interface.go:55-66
                              ? eppk_pick_filtered(p.ctx.get(), rows, m, nullptr, nullptr, 1, picks_.data(), scores_.data(), nullptr)
                          : p.spec.picker == PickerKind::BestScore
                              ? eppk_pick_batch(p.ctx.get(), rows, m, nullptr, picks_.data(), scores_.data())
+                         : p.spec.picker == PickerKind::Bounded
+                             ? eppk_pick_bounded(p.ctx.get(), rows, m, fmask, p.spec.k, nullptr, p.spec.cap_all, p.spec.bounded_policy, nullptr, picks_.data(),
+                                                 scores_.data(), nullptr)
                          : p.spec.picker == PickerKind::WeightedRandom
                              ? eppk_pick_weighted_random(p.ctx.get(), rows, m, fmask, 1, seed + lo, picks_.data(), scores_.data())
                              : eppk_pick_random_topk(p.ctx.get(), rows, m, fmask, p.spec.k, seed + lo, picks_.data(), scores_.data());

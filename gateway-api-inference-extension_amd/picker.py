@@ -197,6 +197,23 @@ def hash_prompt(model: bytes, prompt: bytes, block_chars: int, max_blocks: int) 
     return out[:n]
 
 
+def _bounded_caps(n_pods: int, cap, load):
+    """(cap array or None, cap_all, load array or None) of a bounded pick: `cap` is one int for every pod or a u32 array [n_pods];
+    `load` (optional u32 [n_pods]) is copied, the copy is updated by the call."""
+    cap_arr, cap_all = None, 0
+    if np.ndim(cap) == 0:
+        cap_all = int(cap)
+        if not 0 <= cap_all <= 0xFFFFFFFF:
+            raise EppkError(-1, "bounded pick: cap out of range (u32)")
+    else:
+        cap_arr = np.ascontiguousarray(cap, dtype=np.uint32)
+        assert cap_arr.shape == (n_pods,), "one cap per pod"
+    if load is not None:
+        load = np.array(load, dtype=np.uint32, order="C", copy=True)
+        assert load.shape == (n_pods,), "one load per pod"
+    return cap_arr, cap_all, load
+
+
 class RoundRobinPicker:
     """server.go:84-101 — the reference's picker; the shim's fail-open fallback."""
 
@@ -552,6 +569,50 @@ class BatchedPicker:
         self._check(self._lib.eppk_pick_filtered_device(self._ctx, d_reqs, n_reqs, d_cls or None, d_mask or None, int(k), d_pick, d_score or None,
                                                         d_verdict or None, stream or None), "pick_filtered_device")
 
+    # -- picker "best-score under per-pod caps" (SEMANTICS.md §3d) -----------------------------------
+    def pick_bounded(self, reqs: np.ndarray, k: int, cap, policy: int = _lib.EPPK_BOUNDED_SHED, load: Optional[np.ndarray] = None,
+                     mask: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray]]:
+        """eppk_pick_bounded: every request goes to the best entry of its k ordered fallbacks that still has room.  `cap`: one int
+        for every pod or a u32 array [P]; `load`: the requests each pod already holds (u32 [P], not modified).  Returns ([R] picks,
+        [R] totals, [R] u8 ranks, the loads afterwards or None when no load was given)."""
+        reqs = np.ascontiguousarray(reqs, dtype=np.uint64)
+        assert reqs.ndim == 2 and reqs.shape[1] == self.row_words, "request row stride mismatch"
+        R = reqs.shape[0]
+        mptr = None
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint64)
+            assert mask.shape == (R, (self.n_pods + 63) // 64), "mask shape mismatch"
+            mptr = mask.ctypes.data
+        cap_arr, cap_all, load = _bounded_caps(self.n_pods, cap, load)
+        picks = np.full(R, -1, dtype=np.int32)
+        scores = np.zeros(R, dtype=np.float64)
+        ranks = np.full(R, _lib.EPPK_RANK_NONE, dtype=np.uint8)
+        self._check(self._lib.eppk_pick_bounded(self._ctx, reqs.ctypes.data, R, mptr, int(k), cap_arr.ctypes.data if cap_arr is not None else None,
+                                                cap_all, int(policy), load.ctypes.data if load is not None else None, picks.ctypes.data,
+                                                scores.ctypes.data, ranks.ctypes.data), "pick_bounded")
+        return picks, scores, ranks, load
+
+    def pick_bounded_device(self, d_reqs: int, n_reqs: int, d_mask: Optional[int], k: int, d_cap: Optional[int], cap_all: int, policy: int,
+                            d_load: Optional[int], d_pick: int, d_score: Optional[int], d_rank: Optional[int], stream: int = 0) -> None:
+        """eppk_pick_bounded_device: device pointers as ints (n_reqs entries at d_pick / d_score / d_rank), asynchronous on `stream`."""
+        self._check(self._lib.eppk_pick_bounded_device(self._ctx, d_reqs, n_reqs, d_mask or None, int(k), d_cap or None, int(cap_all), int(policy),
+                                                       d_load or None, d_pick, d_score or None, d_rank or None, stream or None),
+                    "pick_bounded_device")
+
+    def bounded_resolve_device(self, d_lists: int, d_list_scores: Optional[int], n_reqs: int, k: int, d_cap: Optional[int], cap_all: int,
+                               policy: int, d_load: Optional[int], d_pick: int, d_score: Optional[int], d_rank: Optional[int],
+                               stream: int = 0) -> None:
+        """eppk_bounded_resolve_device: the resolve alone, over any [n_reqs][k] lists on the device."""
+        self._check(self._lib.eppk_bounded_resolve_device(self._ctx, d_lists, d_list_scores or None, n_reqs, int(k), d_cap or None, int(cap_all),
+                                                          int(policy), d_load or None, d_pick, d_score or None, d_rank or None, stream or None),
+                    "bounded_resolve_device")
+
+    def bounded_geometry(self) -> Tuple[int, int]:
+        """(rows per chunk, the largest batch the one-launch kernel takes) of the bounded resolve (EPPK_BOUND_CHUNK)."""
+        out = (C.c_uint32 * 2)()
+        self._check(self._lib.eppk_bounded_geometry(self._ctx, out), "bounded_geometry")
+        return int(out[0]), int(out[1])
+
     def set_assumed_load(self, epochs: int) -> None:
         """Assumed load in `epochs` sub-batches per batch (SEMANTICS.md §2b); 0 = off."""
         self._check(self._lib.eppk_set_assumed_load(self._ctx, int(epochs)), "set_assumed_load")
@@ -815,6 +876,20 @@ class DeviceGroup:
         self._check(self._lib.eppk_group_pick_weighted_random(self._g, reqs.ctypes.data, R, mptr, int(k), seed & 0xFFFFFFFFFFFFFFFF, picks.ctypes.data,
                                                               scores.ctypes.data), "group_pick_weighted_random")
         return picks, scores
+
+    def pick_bounded(self, reqs: np.ndarray, k: int, cap, policy: int = _lib.EPPK_BOUNDED_SHED, load: Optional[np.ndarray] = None,
+                     mask: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray]]:
+        """eppk_group_pick_bounded: BatchedPicker.pick_bounded over the group (caps are global across the shards)."""
+        reqs, mask, mptr = self._rows_and_mask(reqs, mask)
+        R = reqs.shape[0]
+        cap_arr, cap_all, load = _bounded_caps(self.n_pods, cap, load)
+        picks = np.full(R, -1, dtype=np.int32)
+        scores = np.zeros(R, dtype=np.float64)
+        ranks = np.full(R, _lib.EPPK_RANK_NONE, dtype=np.uint8)
+        self._check(self._lib.eppk_group_pick_bounded(self._g, reqs.ctypes.data, R, mptr, int(k), cap_arr.ctypes.data if cap_arr is not None else None,
+                                                      cap_all, int(policy), load.ctypes.data if load is not None else None, picks.ctypes.data,
+                                                      scores.ctypes.data, ranks.ctypes.data), "group_pick_bounded")
+        return picks, scores, ranks, load
 
     # -- the pipelined host path over the group (eppk_group_pick_stage_*) ---------------------------------------------
     def stage_buffers(self, which: int, with_mask: bool = False) -> Tuple[np.ndarray, Optional[np.ndarray]]:

@@ -538,6 +538,56 @@ void* eppk_group_stream(eppk_group* g, uint32_t i);      /* member i's hipStream
 /* Device pointer to member i's copy of the gathered picks of the last LEARN / GATHER batch (n_reqs entries, request order). */
 const int32_t* eppk_group_device_picks(eppk_group* g, uint32_t i);
 
+/* ---- picker "best-score under per-pod caps" (SEMANTICS.md §3d) ---------------------------------------------------------------
+ * Every other picker scores a whole batch against one frozen snapshot, so the requests that agree on the best pod all go there: a
+ * traffic spike lands on one pod.  "Track the cost of previously issued requests to avoid overloading servers"
+ * (docs/proposals/006-scheduler/README.md:140; "especially when traffic spikes", :156; prefix affinity "needs to be aware of the
+ * server load", docs/proposals/0602-prefix-cache-aware-routing-proposal/README.md:122): here each pod takes at most cap[p] - load[p]
+ * requests of the batch, and a request that finds its best pod full falls to the next entry of its ordered list.
+ *
+ * The RESOLVE takes any [n_reqs][k] lists (1 <= k <= EPPK_MAX_TOPK) -- eppk_pick_topk_device's, eppk_pick_filtered_device's, the
+ * rounds of eppk_pick_weighted_random_device -- and works in k rounds: in round j every request that is still unassigned bids for entry
+ * j of its list, and of the bidders of pod p the first min(room, bidders) IN BATCH ORDER get it (room = cap[p] - load[p] as the round
+ * before left the loads, 0 when the load is at or above the cap).  An entry outside [0, n_pods) is no bid: EPPK_NO_PICK is legal
+ * anywhere in a list; any other such value is ignored too and raises EPPK_LAUNCH_BAD_PICK.  What no round placed: under
+ * EPPK_BOUNDED_SHED it gets EPPK_NO_PICK / 0.0; under EPPK_BOUNDED_SPILL the first valid entry of its list, whose load grows by one
+ * (modulo 2^32) cap or no cap.  The result is a pure function of the arguments: it depends on no chunk size, grid or CU count.
+ *   d_lists       [n_reqs][k] i32           d_list_scores  nullable [n_reqs][k] f64: the totals of the entries (absent: scores 0.0)
+ *   d_cap         nullable u32 [n_pods]; NULL: every pod's cap is cap_all          (n_pods: that of the latest publish)
+ *   d_load        nullable u32 [n_pods], in / out: the requests each pod holds already; NULL: zeros, and nothing is reported
+ *   d_out_pick    [n_reqs] i32              d_out_score    nullable [n_reqs] f64
+ *   d_out_rank    nullable [n_reqs] u8: the list position that was taken (0 .. k-1); EPPK_RANK_OVERFLOW (| the position under SPILL) for a
+ *                 request no round placed; EPPK_RANK_NONE for one without a valid entry
+ * One pick per request: eppk_index_insert_picks_device takes d_out_pick as it is.  Asynchronous on `stream` (NULL = the context's);
+ * always launches (also under EPPK_RESIDENT=1); ONE stream at a time per context for the bounded entry points (the scratch -- chunk
+ * histograms, lists -- is per context and grows on demand: a call that has to grow it -- the first one, or a larger batch than ever before --
+ * drains the DEVICE first, since queued work may still read the old buffers, so such a call is not asynchronous and cannot be captured
+ * into a graph; run one batch of the largest size before capturing).  Requests are resolved in chunks of EPPK_BOUND_CHUNK rows (environment, read
+ * at eppk_create: a power of two >= 64, default 512); a batch of at most one chunk takes a single launch, a larger one three per
+ * round and one more.  Errors: EPPK_ERR_ARG for a null argument, k outside 1..EPPK_MAX_TOPK, an unknown policy, or while assumed load
+ * is on (eppk_set_assumed_load: both count load; they do not combine); EPPK_ERR_NO_SNAPSHOT; the host-buffer forms EPPK_ERR_LIMIT for
+ * n_reqs > max_batch. */
+#define EPPK_BOUNDED_SHED   0u     /* a request no round placed is shed: EPPK_NO_PICK (-> 503 / retry) */
+#define EPPK_BOUNDED_SPILL  1u     /* ... goes to the first valid entry of its list, above the cap */
+#define EPPK_RANK_OVERFLOW  0x40u
+#define EPPK_RANK_NONE      0x80u
+int eppk_bounded_resolve_device(eppk_ctx* ctx, const int32_t* d_lists, const double* d_list_scores, uint32_t n_reqs, uint32_t k,
+                                const uint32_t* d_cap, uint32_t cap_all, uint32_t policy, uint32_t* d_load, int32_t* d_out_pick,
+                                double* d_out_score, uint8_t* d_out_rank, void* stream);
+/* eppk_pick_topk_device into the context's scratch, then the resolve. */
+int eppk_pick_bounded_device(eppk_ctx* ctx, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, uint32_t k,
+                             const uint32_t* d_cap, uint32_t cap_all, uint32_t policy, uint32_t* d_load, int32_t* d_out_pick,
+                             double* d_out_score, uint8_t* d_out_rank, void* stream);
+/* Host buffers in and out (rows checked as by eppk_pick_batch; cap, load, out_score and out_rank nullable as above). */
+int eppk_pick_bounded(eppk_ctx* ctx, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint32_t* cap,
+                      uint32_t cap_all, uint32_t policy, uint32_t* load, int32_t* out_pick, double* out_score, uint8_t* out_rank);
+/* Over a group: eppk_group_pick_topk gathers the lists on the host, member 0 resolves them.  Caps are global, not per shard: the
+ * result equals eppk_pick_bounded on the unsharded batch bit for bit. */
+int eppk_group_pick_bounded(eppk_group* g, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint32_t* cap,
+                            uint32_t cap_all, uint32_t policy, uint32_t* load, int32_t* out_pick, double* out_score, uint8_t* out_rank);
+/* Diagnostic: out = {rows per chunk, the largest n_reqs the one-launch kernel takes}. */
+int eppk_bounded_geometry(const eppk_ctx* ctx, uint32_t out[2]);
+
 /* ---- adjacent host-side steps of the same path ---------------------------------------------- */
 
 /* Chain-hash a prompt into block hashes (0602-…/README.md:99): XXH64, seed 0,

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Register / LDS / spill figures of the pick-kernel instantiations, from hipcc's -Rpass-analysis=kernel-resource-usage
-(CPU only: cross-compiles for gfx950).  `python scripts/kernel_resources.py [u64_6] [filter-substring]`."""
+(CPU only: cross-compiles for gfx950).  `python scripts/kernel_resources.py [u64_6] [filter-substring]`; a unit that ends in .hip is
+taken as the file's name: `python scripts/kernel_resources.py eppk.hip bounded_` (the kernels of csrc/eppk_bounded.hip.h)."""
 import os
 import re
 import subprocess
@@ -12,7 +13,7 @@ unit = sys.argv[1] if len(sys.argv) > 1 else "u64_6"
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
 extra = sys.argv[3:]
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-c", "-o", "/tmp/_kr.o",
-       f"eppk_pick_{unit}.hip", "-Rpass-analysis=kernel-resource-usage", *extra]
+       unit if unit.endswith(".hip") else f"eppk_pick_{unit}.hip", "-Rpass-analysis=kernel-resource-usage", *extra]
 out = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True).stderr
 cur = None
 rows = {}
@@ -29,4 +30,4 @@ for line in out.splitlines():
 for k, v in rows.items():
     if flt in k:
         print(f"{k:110s} VGPR {v.get('VGPRs')} SGPR {v.get('TotalSGPRs')} occ {v.get('Occupancy [waves/SIMD]')} scratch {v.get('ScratchSize [bytes/lane]')} "
-              f"spillS {v.get('SGPRs Spill')} spillV {v.get('VGPRs Spill')}")
+              f"spillS {v.get('SGPRs Spill')} spillV {v.get('VGPRs Spill')} lds {v.get('LDS Size [bytes/block]')}")
