@@ -10,6 +10,7 @@
 #include "eppk_pick_inst.hip.h"
 #include "eppk_filter.hip.h"
 #include "eppk_bounded.hip.h"
+#include "eppk_banded.hip.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -21,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <dlfcn.h>
+#include <functional>
 #include <initializer_list>
 #include <map>
 #include <mutex>
@@ -201,6 +203,10 @@ struct eppk_ctx {
   uint32_t* d_bd_pods = nullptr;                            // [4][EPPK_MAX_PODS]: room, load (no d_load), and the host forms' cap and load
   int32_t* d_bd_list = nullptr; double* d_bd_lscore = nullptr; size_t bd_list_rows = 0;   // lists of eppk_pick_bounded_device (x EPPK_MAX_TOPK)
   int32_t* d_bd_opick = nullptr; double* d_bd_oscore = nullptr; uint8_t* d_bd_orank = nullptr; size_t bd_out_rows = 0;   // results of the host forms
+  // ... with priority bands (SEMANTICS.md §3e; eppk_banded.hip.h): the band order of a batch of more than one chunk
+  uint32_t* d_bn_perm = nullptr; size_t bn_perm_rows = 0;   // place in the band order -> request
+  uint32_t* d_bn_bh = nullptr; size_t bn_bh_words = 0;      // seg[0 .. 8] (kBandSegWords words), then [chunks][8] rows per band / their offsets
+  uint8_t* d_bn_band = nullptr; size_t bn_band_rows = 0;    // band bytes of the host forms
 
   // measurement
   bool prof = false;
@@ -1501,6 +1507,7 @@ void eppk_destroy(eppk_ctx* c) {
   (void)hipFree(c->d_fplanes); (void)hipFree(c->d_fmask); (void)hipFree(c->d_fcls); (void)hipFree(c->d_fverdict);
   (void)hipFree(c->d_bd_hist); (void)hipFree(c->d_bd_state); (void)hipFree(c->d_bd_pods); (void)hipFree(c->d_bd_list); (void)hipFree(c->d_bd_lscore);
   (void)hipFree(c->d_bd_opick); (void)hipFree(c->d_bd_oscore); (void)hipFree(c->d_bd_orank);
+  (void)hipFree(c->d_bn_perm); (void)hipFree(c->d_bn_bh); (void)hipFree(c->d_bn_band);
   (void)hipFree(c->d_rows); (void)hipFree(c->d_rm); (void)hipFree(c->d_rs_pick); (void)hipFree(c->d_rs_score); (void)hipFree(c->d_learn);
   if (c->h_reqs) (void)hipHostFree(c->h_reqs);
   if (c->h_mask) (void)hipHostFree(c->h_mask);
@@ -3032,9 +3039,11 @@ int bounded_resolve(eppk_ctx* c, const int32_t* d_lists, const double* d_scores,
   return EPPK_OK;
 }
 
-// Host buffers around the resolve: cap and load up, the resolve over device lists on the context's stream, results (and load) down.
-int bounded_host_finish(eppk_ctx* c, const int32_t* d_lists, const double* d_scores, uint32_t n_reqs, uint32_t k, const uint32_t* cap, uint32_t cap_all,
-                        uint32_t policy, uint32_t* load, int32_t* out_pick, double* out_score, uint8_t* out_rank) {
+// Host buffers around a resolve: cap and load up, resolve(d_cap, d_load, d_out_pick, d_out_score, d_out_rank) over device lists on the
+// context's stream, results (and load) down.
+using BoundResolveFn = std::function<int(const uint32_t* d_cap, uint32_t* d_load, int32_t* d_out_pick, double* d_out_score, uint8_t* d_out_rank)>;
+int bounded_host_around(eppk_ctx* c, uint32_t n_reqs, const uint32_t* cap, uint32_t* load, int32_t* out_pick, double* out_score, uint8_t* out_rank,
+                        const BoundResolveFn& resolve) {
   int rc = bounded_pod_scratch(c);
   if (rc) return rc;
   if ((rc = bounded_grow(c, &c->bd_out_rows, bounded_rows(c, n_reqs),
@@ -3044,8 +3053,7 @@ int bounded_host_finish(eppk_ctx* c, const int32_t* d_lists, const double* d_sco
   const size_t pod_bytes = (size_t)c->n_pods * sizeof(uint32_t);
   if (cap && pod_bytes) HIPCHK(c, hipMemcpyAsync(d_cap, cap, pod_bytes, hipMemcpyHostToDevice, c->stream));
   if (load && pod_bytes) HIPCHK(c, hipMemcpyAsync(d_load, load, pod_bytes, hipMemcpyHostToDevice, c->stream));
-  rc = bounded_resolve(c, d_lists, d_scores, n_reqs, k, cap ? d_cap : nullptr, cap_all, policy, load ? d_load : nullptr, c->d_bd_opick,
-                       out_score ? c->d_bd_oscore : nullptr, c->d_bd_orank, c->stream);
+  rc = resolve(cap ? d_cap : nullptr, load ? d_load : nullptr, c->d_bd_opick, out_score ? c->d_bd_oscore : nullptr, c->d_bd_orank);
   if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(out_pick, c->d_bd_opick, (size_t)n_reqs * 4u, hipMemcpyDeviceToHost, c->stream));
   if (out_score) HIPCHK(c, hipMemcpyAsync(out_score, c->d_bd_oscore, (size_t)n_reqs * 8u, hipMemcpyDeviceToHost, c->stream));
@@ -3053,6 +3061,14 @@ int bounded_host_finish(eppk_ctx* c, const int32_t* d_lists, const double* d_sco
   if (load && pod_bytes) HIPCHK(c, hipMemcpyAsync(load, d_load, pod_bytes, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return EPPK_OK;
+}
+
+int bounded_host_finish(eppk_ctx* c, const int32_t* d_lists, const double* d_scores, uint32_t n_reqs, uint32_t k, const uint32_t* cap, uint32_t cap_all,
+                        uint32_t policy, uint32_t* load, int32_t* out_pick, double* out_score, uint8_t* out_rank) {
+  return bounded_host_around(c, n_reqs, cap, load, out_pick, out_score, out_rank,
+                             [&](const uint32_t* d_cap, uint32_t* d_load, int32_t* d_pick, double* d_score, uint8_t* d_rank) {
+                               return bounded_resolve(c, d_lists, d_scores, n_reqs, k, d_cap, cap_all, policy, d_load, d_pick, d_score, d_rank, c->stream);
+                             });
 }
 
 int bounded_lists(eppk_ctx* c, uint32_t n_reqs) {
@@ -3088,15 +3104,10 @@ int eppk_pick_bounded_device(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, c
                          stream ? (hipStream_t)stream : c->stream);
 }
 
-int eppk_pick_bounded(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint32_t* cap, uint32_t cap_all,
-                      uint32_t policy, uint32_t* load, int32_t* out_pick, double* out_score, uint8_t* out_rank) {
-  if (!c || ((!reqs || !out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_bounded: null argument");
-  int rc = bounded_check(c, "eppk_pick_bounded", k, policy);
-  if (rc) return rc;
-  if (n_reqs > c->cfg.max_batch) return fail(c, EPPK_ERR_LIMIT, "eppk_pick_bounded: n_reqs > max_batch");
-  if (n_reqs == 0) return EPPK_OK;
-  if ((rc = validate_rows(c, "eppk_pick_bounded", reqs, n_reqs))) return rc;
-  HIPCHK(c, hipSetDevice(c->cfg.device));
+namespace {
+// The top-k lists of a host form's batch into d_tk_pick / d_tk_score, on the context's stream (rows checked by the caller).
+int bounded_host_lists(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k) {
+  int rc;
   const size_t J = (c->n_pods + 63u) / 64u;
   const bool masked = cand_mask != nullptr && J != 0u;
   if ((rc = topk_ensure(c, masked))) return rc;
@@ -3109,6 +3120,20 @@ int eppk_pick_bounded(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint
     if ((rc = run_pick(c, (const uint8_t*)c->d_tk_reqs, n_reqs, masked ? c->d_tk_mask : nullptr, c->d_tk_pick, c->d_tk_score, c->stream, k, false, 0ull, 0u)))
       return rc;
   }
+  return EPPK_OK;
+}
+}  // namespace
+
+int eppk_pick_bounded(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint32_t* cap, uint32_t cap_all,
+                      uint32_t policy, uint32_t* load, int32_t* out_pick, double* out_score, uint8_t* out_rank) {
+  if (!c || ((!reqs || !out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_bounded: null argument");
+  int rc = bounded_check(c, "eppk_pick_bounded", k, policy);
+  if (rc) return rc;
+  if (n_reqs > c->cfg.max_batch) return fail(c, EPPK_ERR_LIMIT, "eppk_pick_bounded: n_reqs > max_batch");
+  if (n_reqs == 0) return EPPK_OK;
+  if ((rc = validate_rows(c, "eppk_pick_bounded", reqs, n_reqs))) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if ((rc = bounded_host_lists(c, reqs, n_reqs, cand_mask, k))) return rc;
   return bounded_host_finish(c, c->d_tk_pick, c->d_tk_score, n_reqs, k, cap, cap_all, policy, load, out_pick, out_score, out_rank);
 }
 
@@ -3117,6 +3142,171 @@ int eppk_bounded_geometry(const eppk_ctx* c, uint32_t out[2]) {
   out[0] = c->bound_chunk;
   out[1] = c->bound_chunk;
   return EPPK_OK;
+}
+
+// ---- ... with priority bands (SEMANTICS.md §3e; eppk_banded.hip.h) -----------------------------------------------------------
+
+namespace {
+
+// The arguments every banded entry point shares; the table as the kernels take it.
+int banded_check(eppk_ctx* c, const char* who, uint32_t k, const eppk_band_table* t, eppk::BandTab* tab) {
+  if (!t) return fail(c, EPPK_ERR_ARG, std::string(who) + ": null band table");
+  const int rc = bounded_check(c, who, k, EPPK_BOUNDED_SHED);
+  if (rc) return rc;
+  if (t->n_bands < 1u || t->n_bands > EPPK_MAX_BANDS) return fail(c, EPPK_ERR_ARG, std::string(who) + ": n_bands out of range (1..8)");
+  *tab = eppk::BandTab{};
+  tab->n_bands = t->n_bands;
+  for (uint32_t b = 0; b < t->n_bands; ++b) {
+    if (t->policy[b] != EPPK_BOUNDED_SHED && t->policy[b] != EPPK_BOUNDED_SPILL)
+      return fail(c, EPPK_ERR_ARG, std::string(who) + ": unknown policy " + std::to_string(t->policy[b]) + " in band " + std::to_string(b));
+    if (b && t->reserve[b] < t->reserve[b - 1u])
+      return fail(c, EPPK_ERR_ARG, std::string(who) + ": the reserve of band " + std::to_string(b) + " is below that of band " + std::to_string(b - 1u) +
+                                       " (reserves must not decrease)");
+    if (t->policy[b] == EPPK_BOUNDED_SPILL) tab->spill |= 1u << b;
+    tab->reserve[b] = t->reserve[b];
+  }
+  return EPPK_OK;
+}
+
+// Band bytes of a host form, before anything is launched: checked as the class bytes of §2c are, and counted per band.
+int banded_host_counts(eppk_ctx* c, const char* who, const uint8_t* band, uint32_t n_reqs, uint32_t n_bands, uint32_t counts[EPPK_MAX_BANDS]) {
+  for (uint32_t b = 0; b < EPPK_MAX_BANDS; ++b) counts[b] = 0u;
+  if (!band) { counts[0] = n_reqs; return EPPK_OK; }
+  for (uint32_t r = 0; r < n_reqs; ++r) {
+    if (band[r] >= n_bands)
+      return fail(c, EPPK_ERR_ARG, std::string(who) + ": request row " + std::to_string(r) + " names band " + std::to_string(band[r]) + " of " +
+                                       std::to_string(n_bands));
+    ++counts[band[r]];
+  }
+  return EPPK_OK;
+}
+
+// The launches of the banded resolve on `st` (arguments checked by the caller; n_reqs != 0).  `counts`: the rows per band where the host
+// knows them (the launches of an empty band are skipped, the grids fit the band), else nullptr: every band is launched as wide as the
+// batch, and what lies past the band's last chunk exits on the device.
+int banded_resolve(eppk_ctx* c, const int32_t* d_lists, const double* d_scores, uint32_t n_reqs, uint32_t k, const uint8_t* d_band, const eppk::BandTab& tab,
+                   const uint32_t* counts, const uint32_t* d_cap, uint32_t cap_all, uint32_t* d_load, int32_t* d_out_pick, double* d_out_score,
+                   uint8_t* d_out_rank, hipStream_t st) {
+  const uint32_t P = c->n_pods, chunk = c->bound_chunk;
+  uint8_t* state = d_out_rank;
+  if (!state) {
+    const int rc = bounded_grow(c, &c->bd_state_rows, bounded_rows(c, n_reqs), {{(void**)&c->d_bd_state, 1u}});
+    if (rc) return rc;
+    state = c->d_bd_state;
+  }
+  if (n_reqs <= chunk) {
+    hipLaunchKernelGGL(eppk::banded_resolve_one_kernel, dim3(1), dim3(eppk::kBoundThreads), 0, st, d_lists, d_scores, n_reqs, k, P, d_band, tab, d_cap, cap_all,
+                       d_load, d_out_pick, d_out_score, state, c->d_status);
+    HIPCHK(c, hipGetLastError());
+    return EPPK_OK;
+  }
+  const uint32_t n_chunks = (uint32_t)(((uint64_t)n_reqs + chunk - 1u) / chunk);
+  int rc = bounded_pod_scratch(c);
+  if (rc) return rc;
+  if ((rc = bounded_grow(c, &c->bd_hist_words, (size_t)n_chunks * P, {{(void**)&c->d_bd_hist, sizeof(uint32_t)}}))) return rc;
+  if ((rc = bounded_grow(c, &c->bn_perm_rows, bounded_rows(c, n_reqs), {{(void**)&c->d_bn_perm, sizeof(uint32_t)}}))) return rc;
+  if ((rc = bounded_grow(c, &c->bn_bh_words, eppk::kBandSegWords + (size_t)n_chunks * EPPK_MAX_BANDS, {{(void**)&c->d_bn_bh, sizeof(uint32_t)}}))) return rc;
+  uint32_t* seg = c->d_bn_bh;
+  uint32_t* bh = c->d_bn_bh + eppk::kBandSegWords;
+  uint32_t* perm = c->d_bn_perm;
+  uint32_t* room = c->d_bd_pods;
+  uint32_t* load = d_load;
+  if (!load) {
+    load = c->d_bd_pods + EPPK_MAX_PODS;
+    HIPCHK(c, hipMemsetAsync(load, 0, (size_t)EPPK_MAX_PODS * sizeof(uint32_t), st));
+  }
+  HIPCHK(c, hipMemsetAsync(state, (int)eppk::kBoundUnassigned, n_reqs, st));
+  // grid-stride loops as wide as the CUs this context may use (EPPK_MAX_CU): the results do not depend on the width
+  const uint32_t wide = (uint32_t)c->num_cu * 4u;
+  const uint32_t chunk_grid = n_chunks < wide ? n_chunks : wide;
+  const uint32_t pod_wgs = (P + eppk::kBoundScanPods - 1u) / eppk::kBoundScanPods, pod_grid = pod_wgs < wide ? pod_wgs : wide;
+  const uint32_t row_wgs = (uint32_t)(((uint64_t)n_reqs + eppk::kBoundThreads - 1u) / eppk::kBoundThreads), row_grid = row_wgs < wide * 2u ? row_wgs : wide * 2u;
+  hipLaunchKernelGGL(eppk::banded_hist_kernel, dim3(chunk_grid), dim3(eppk::kBoundThreads), 0, st, d_band, n_reqs, tab.n_bands, chunk, n_chunks, bh);
+  hipLaunchKernelGGL(eppk::banded_offsets_kernel, dim3(1), dim3(eppk::kBoundThreads), 0, st, bh, n_chunks, seg);
+  hipLaunchKernelGGL(eppk::banded_scatter_kernel, dim3(chunk_grid), dim3(64), 0, st, d_band, n_reqs, tab.n_bands, chunk, n_chunks, (const uint32_t*)bh, perm);
+  if (P) for (uint32_t b = 0; b < tab.n_bands; ++b) {
+    uint32_t band_grid = chunk_grid;
+    if (counts) {
+      if (!counts[b]) continue;
+      const uint32_t band_chunks = (uint32_t)(((uint64_t)counts[b] + chunk - 1u) / chunk);
+      band_grid = band_chunks < wide ? band_chunks : wide;
+    }
+    for (uint32_t j = 0; j < k; ++j) {
+      hipLaunchKernelGGL(eppk::banded_count_kernel, dim3(band_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, k, j, P, chunk, (const uint32_t*)seg, b,
+                         (const uint32_t*)perm, (const uint8_t*)state, c->d_bd_hist);
+      hipLaunchKernelGGL(eppk::banded_scan_kernel, dim3(pod_grid), dim3(eppk::kBoundScanSegs * eppk::kBoundScanPods), 0, st, c->d_bd_hist, chunk,
+                         (const uint32_t*)seg, b, P, d_cap, cap_all, tab.reserve[b], load, room);
+      hipLaunchKernelGGL(eppk::banded_assign_kernel, dim3(band_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, d_scores, k, j, P, chunk, (const uint32_t*)seg,
+                         b, (const uint32_t*)perm, (const uint32_t*)c->d_bd_hist, (const uint32_t*)room, state, d_out_pick, d_out_score);
+    }
+  }
+  hipLaunchKernelGGL(eppk::banded_finish_kernel, dim3(row_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, d_scores, n_reqs, k, P, d_band, tab.n_bands, tab.spill,
+                     load, state, d_out_pick, d_out_score, c->d_status);
+  HIPCHK(c, hipGetLastError());
+  return EPPK_OK;
+}
+
+// The band bytes up (checked and counted by banded_host_counts), then as bounded_host_finish.
+int banded_host_finish(eppk_ctx* c, const int32_t* d_lists, const double* d_scores, uint32_t n_reqs, uint32_t k, const uint8_t* band,
+                       const uint32_t* counts, const eppk::BandTab& tab, const uint32_t* cap, uint32_t cap_all, uint32_t* load, int32_t* out_pick,
+                       double* out_score, uint8_t* out_rank) {
+  if (band) {
+    const int rc = bounded_grow(c, &c->bn_band_rows, bounded_rows(c, n_reqs), {{(void**)&c->d_bn_band, 1u}});
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_bn_band, band, n_reqs, hipMemcpyHostToDevice, c->stream));
+  }
+  return bounded_host_around(c, n_reqs, cap, load, out_pick, out_score, out_rank,
+                             [&](const uint32_t* d_cap, uint32_t* d_load, int32_t* d_pick, double* d_score, uint8_t* d_rank) {
+                               return banded_resolve(c, d_lists, d_scores, n_reqs, k, band ? c->d_bn_band : nullptr, tab, counts, d_cap, cap_all, d_load,
+                                                     d_pick, d_score, d_rank, c->stream);
+                             });
+}
+
+}  // namespace
+
+int eppk_banded_resolve_device(eppk_ctx* c, const int32_t* d_lists, const double* d_list_scores, uint32_t n_reqs, uint32_t k, const uint8_t* d_band,
+                               const eppk_band_table* bands, const uint32_t* d_cap, uint32_t cap_all, uint32_t* d_load, int32_t* d_out_pick,
+                               double* d_out_score, uint8_t* d_out_rank, void* stream) {
+  if (!c || ((!d_lists || !d_out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_banded_resolve_device: null argument");
+  eppk::BandTab tab;
+  const int rcc = banded_check(c, "eppk_banded_resolve_device", k, bands, &tab);
+  if (rcc) return rcc;
+  if (n_reqs == 0) return EPPK_OK;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  return banded_resolve(c, d_lists, d_list_scores, n_reqs, k, d_band, tab, nullptr, d_cap, cap_all, d_load, d_out_pick, d_out_score, d_out_rank,
+                        stream ? (hipStream_t)stream : c->stream);
+}
+
+int eppk_pick_banded_device(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, uint32_t k, const uint8_t* d_band,
+                            const eppk_band_table* bands, const uint32_t* d_cap, uint32_t cap_all, uint32_t* d_load, int32_t* d_out_pick,
+                            double* d_out_score, uint8_t* d_out_rank, void* stream) {
+  if (!c || ((!d_reqs || !d_out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_banded_device: null argument");
+  eppk::BandTab tab;
+  int rc = banded_check(c, "eppk_pick_banded_device", k, bands, &tab);
+  if (rc) return rc;
+  if (n_reqs == 0) return EPPK_OK;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if ((rc = bounded_lists(c, n_reqs))) return rc;
+  if ((rc = eppk_pick_topk_device(c, d_reqs, n_reqs, d_cand_mask, k, c->d_bd_list, c->d_bd_lscore, stream))) return rc;
+  return banded_resolve(c, c->d_bd_list, c->d_bd_lscore, n_reqs, k, d_band, tab, nullptr, d_cap, cap_all, d_load, d_out_pick, d_out_score, d_out_rank,
+                        stream ? (hipStream_t)stream : c->stream);
+}
+
+int eppk_pick_banded(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint8_t* band,
+                     const eppk_band_table* bands, const uint32_t* cap, uint32_t cap_all, uint32_t* load, int32_t* out_pick, double* out_score,
+                     uint8_t* out_rank) {
+  if (!c || ((!reqs || !out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_banded: null argument");
+  eppk::BandTab tab;
+  int rc = banded_check(c, "eppk_pick_banded", k, bands, &tab);
+  if (rc) return rc;
+  if (n_reqs > c->cfg.max_batch) return fail(c, EPPK_ERR_LIMIT, "eppk_pick_banded: n_reqs > max_batch");
+  if (n_reqs == 0) return EPPK_OK;
+  if ((rc = validate_rows(c, "eppk_pick_banded", reqs, n_reqs))) return rc;
+  uint32_t counts[EPPK_MAX_BANDS];
+  if ((rc = banded_host_counts(c, "eppk_pick_banded", band, n_reqs, tab.n_bands, counts))) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if ((rc = bounded_host_lists(c, reqs, n_reqs, cand_mask, k))) return rc;
+  return banded_host_finish(c, c->d_tk_pick, c->d_tk_score, n_reqs, k, band, counts, tab, cap, cap_all, load, out_pick, out_score, out_rank);
 }
 
 // ---- on-device prompt hashing ------------------------------------------------------------------------
@@ -3759,6 +3949,33 @@ int eppk_group_pick_bounded(eppk_group* g, const void* reqs, uint32_t n_reqs, co
       hipMemcpyAsync(c0->d_bd_lscore, totals.data(), totals.size() * 8u, hipMemcpyHostToDevice, c0->stream) != hipSuccess)
     return gfail(g, EPPK_ERR_DEVICE, "eppk_group_pick_bounded: upload failed");
   if ((rc = bounded_host_finish(c0, c0->d_bd_list, c0->d_bd_lscore, n_reqs, k, cap, cap_all, policy, load, out_pick, out_score, out_rank))) return mfail(rc);
+  return EPPK_OK;
+}
+
+int eppk_group_pick_banded(eppk_group* g, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint8_t* band,
+                           const eppk_band_table* bands, const uint32_t* cap, uint32_t cap_all, uint32_t* load, int32_t* out_pick,
+                           double* out_score, uint8_t* out_rank) {
+  if (!g || ((!reqs || !out_pick) && n_reqs)) return gfail(g, EPPK_ERR_ARG, "eppk_group_pick_banded: null argument");
+  eppk_ctx* c0 = g->ctx[0];
+  eppk::BandTab tab;
+  uint32_t counts[EPPK_MAX_BANDS];
+  int rc = banded_check(c0, "eppk_group_pick_banded", k, bands, &tab);
+  if (!rc) rc = banded_host_counts(c0, "eppk_group_pick_banded", band, n_reqs, tab.n_bands, counts);
+  if (rc) return gfail(g, rc, eppk_last_error(c0));
+  // as eppk_group_pick_bounded: the lists of the whole batch on the host, then ONE resolve on member 0
+  std::vector<int32_t> lists((size_t)n_reqs * k);
+  std::vector<double> totals((size_t)n_reqs * k);
+  if ((rc = group_topk(g, "eppk_group_pick_banded", reqs, n_reqs, cand_mask, k, false, 0ull, lists.data(), totals.data()))) return rc;
+  if (n_reqs == 0) return EPPK_OK;
+  auto mfail = [&](int code) { return gfail(g, code, "device " + std::to_string(g->dev[0]) + ": " + eppk_last_error(c0)); };
+  if (hipSetDevice(g->dev[0]) != hipSuccess) return gfail(g, EPPK_ERR_DEVICE, "eppk_group_pick_banded: hipSetDevice failed");
+  if ((rc = bounded_lists(c0, n_reqs))) return mfail(rc);
+  if (hipMemcpyAsync(c0->d_bd_list, lists.data(), lists.size() * 4u, hipMemcpyHostToDevice, c0->stream) != hipSuccess ||
+      hipMemcpyAsync(c0->d_bd_lscore, totals.data(), totals.size() * 8u, hipMemcpyHostToDevice, c0->stream) != hipSuccess)
+    return gfail(g, EPPK_ERR_DEVICE, "eppk_group_pick_banded: upload failed");
+  if ((rc = banded_host_finish(c0, c0->d_bd_list, c0->d_bd_lscore, n_reqs, k, band, counts, tab, cap, cap_all, load, out_pick,
+                               out_score, out_rank)))
+    return mfail(rc);
   return EPPK_OK;
 }
 

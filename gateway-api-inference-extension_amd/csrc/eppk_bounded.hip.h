@@ -50,23 +50,32 @@ struct BoundRoomArray {
   __device__ __forceinline__ uint32_t operator()(uint32_t p) const { return room[p]; }
 };
 
-// ONE wavefront takes rows [r0, r1) through round j, 64 rows per trip in ascending order.  cnt[] (LDS, one counter per pod) holds, for
-// every pod, the number of this round's bidders in front of the row the wavefront is at: the caller sets it for r0, every trip carries
-// it on.  Within a trip the lanes that bid for one pod find each other by ballot; a lane's place is the counter plus the bidding lanes
+// The request at place i of the order the wavefront walks: the batch's own order here; eppk_banded.hip.h walks a permutation.
+struct BoundRowSelf {
+  __device__ __forceinline__ uint64_t operator()(uint64_t i) const { return i; }
+};
+
+// ONE wavefront takes places [r0, r1) through round j, 64 per trip in ascending order; place i holds request row(i).  cnt[] (LDS, one
+// counter per pod) holds, for every pod, the number of this round's bidders in front of the place the wavefront is at: the caller sets
+// it for r0, every trip carries it on.  Within a trip the lanes that bid for one pod find each other by ballot; a lane's place is the counter plus the bidding lanes
 // below it.  Every index into cnt[] has passed bounded_valid (p < n_pods <= EPPK_MAX_PODS).
-template <class Room>
+template <class Room, class Row = BoundRowSelf>
 __device__ __forceinline__ void bounded_wave_round(const int32_t* __restrict__ lists, const double* __restrict__ scores, uint32_t k, uint32_t j,
                                                    uint64_t r0, uint64_t r1, uint32_t n_pods, uint32_t* cnt, const Room room,
-                                                   uint8_t* state, int32_t* __restrict__ out_pick, double* __restrict__ out_score) {
+                                                   uint8_t* state, int32_t* __restrict__ out_pick, double* __restrict__ out_score,
+                                                   const Row row = Row{}) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint64_t below = (1ull << lane) - 1ull;
   for (uint64_t t0 = r0; t0 < r1; t0 += 64u) {
-    const uint64_t r = t0 + lane;
+    uint64_t r = t0 + lane;
     int32_t e = EPPK_NO_PICK;
     bool bid = false;
-    if (r < r1 && state[r] == kBoundUnassigned) {
-      e = lists[r * k + j];
-      bid = bounded_valid(e, n_pods);
+    if (r < r1) {
+      r = row(r);
+      if (state[r] == kBoundUnassigned) {
+        e = lists[r * k + j];
+        bid = bounded_valid(e, n_pods);
+      }
     }
     bool take = false;
     for (uint64_t todo = __ballot(bid); todo != 0ull;) {            // (wave-uniform: one trip of this loop per distinct pod)

@@ -716,6 +716,7 @@ inline eppk_cfg MakeCfg(const SchedulerProfile& profile, const GpuPickerOptions&
 struct Request {  // interface.go:35-44
   std::string request_id, target_model, prompt;
   std::map<std::string, std::string> headers;
+  uint8_t band = 0;                              // priority band, 0 = the most important (SEMANTICS.md §3e); read by a Bounded profile with bands
 };
 
 struct ScoredEndpoint {  // interface.go:50-53
@@ -732,6 +733,9 @@ enum class PickerKind { BestScore, RandomTopK, WeightedRandom, Bounded };   // e
                                                                    // weighted-random: 006-scheduler/README.md:154 (SEMANTICS.md §3c); bounded:
                                                                    // best-score under per-pod caps, 006-scheduler/README.md:140 (SEMANTICS.md §3d)
 
+struct eppk_band { uint32_t policy = EPPK_BOUNDED_SHED, reserve = 0; };   // one entry of eppk_band_table: what becomes of the band's overflow, and
+                                                                          // the slots of every endpoint the band may not use
+
 struct ProfileSpec {
   std::string name;
   std::function<bool(const Endpoint&)> filter;   // conjunction of the profile's Filter plugins (interface.go:113-118); empty = all
@@ -742,6 +746,8 @@ struct ProfileSpec {
   uint32_t cap_all = 0;                          // bounded: requests of ONE batch handed to the library any endpoint takes at most; MUST be set
                                                  // (Configure refuses 0)
   uint32_t bounded_policy = EPPK_BOUNDED_SHED;   // bounded: what becomes of a request that finds every entry full (SHED: Unavailable)
+  std::vector<eppk_band> bands;                  // bounded: priority bands, band 0 first (SEMANTICS.md §3e); Request::band picks the entry, and
+                                                 // bounded_policy is not read.  Empty = no bands: batch order alone decides (§3d)
   std::vector<eppk_predicate> predicates;        // metric predicates behind `filter` (SEMANTICS.md §2c): ONE program, evaluated on the device
                                                  // against the gauges of the snapshot; empty = none.  A request they shed gets Unavailable.
 };
@@ -793,6 +799,10 @@ class Scheduler {  // interface.go:55-66
       GpuPickerOptions go; go.max_pods = opt.max_pods; go.max_blocks = opt.max_blocks; go.max_batch = opt.max_batch;
       // (a cap of 0 leaves no room on any endpoint: every request would end as Unavailable -- a profile that forgot to set it)
       if (ps.picker == PickerKind::Bounded && ps.cap_all == 0) return {Code::Internal, std::string("profile ") + ps.name + ": the bounded picker needs cap_all > 0"};
+      if (ps.bands.size() > EPPK_MAX_BANDS) return {Code::Internal, std::string("profile ") + ps.name + ": more than 8 bands"};
+      for (size_t b = 1; b < ps.bands.size(); ++b)
+        if (ps.bands[b].reserve < ps.bands[b - 1].reserve)
+          return {Code::Internal, std::string("profile ") + ps.name + ": the reserve of band " + std::to_string(b) + " is below that of band " + std::to_string(b - 1)};
       eppk_cfg cfg = MakeCfg(sp, go, opt.index_slots, opt.device);
       eppk_ctx* c = nullptr;
       if (eppk_create(&cfg, &c) != EPPK_OK) return {Code::Internal, std::string("profile ") + ps.name + ": " + eppk_last_error(nullptr)};
@@ -884,11 +894,23 @@ class Scheduler {  // interface.go:55-66
             if (eppk_filter_masks(p.ctx.get(), rows, m, nullptr, nullptr, fmask_.data(), nullptr) != EPPK_OK) return {Code::Internal, eppk_last_error(p.ctx.get())};
             fmask = fmask_.data();
           }
+          const bool banded = p.spec.picker == PickerKind::Bounded && !p.spec.bands.empty();
+          eppk_band_table table;
+          if (banded) {
+            std::memset(&table, 0, sizeof table);
+            table.n_bands = (uint32_t)p.spec.bands.size();
+            for (size_t b = 0; b < p.spec.bands.size(); ++b) { table.policy[b] = p.spec.bands[b].policy; table.reserve[b] = p.spec.bands[b].reserve; }
+            bands_.resize(m);
+            for (uint32_t i = 0; i < m; ++i) bands_[i] = requests[idx[lo + i]].band;   // (a band the table does not have: the library refuses the batch)
+          }
           const int rc = staged ? eppk_pick_batch_staged(p.ctx.get(), m, 0, picks_.data(), scores_.data())
                          : filtered && p.spec.picker == PickerKind::BestScore
                              ? eppk_pick_filtered(p.ctx.get(), rows, m, nullptr, nullptr, 1, picks_.data(), scores_.data(), nullptr)
                          : p.spec.picker == PickerKind::BestScore
                              ? eppk_pick_batch(p.ctx.get(), rows, m, nullptr, picks_.data(), scores_.data())
+                         : banded
+                             ? eppk_pick_banded(p.ctx.get(), rows, m, fmask, p.spec.k, bands_.data(), &table, nullptr, p.spec.cap_all, nullptr, picks_.data(),
+                                                scores_.data(), nullptr)
                          : p.spec.picker == PickerKind::Bounded
                              ? eppk_pick_bounded(p.ctx.get(), rows, m, fmask, p.spec.k, nullptr, p.spec.cap_all, p.spec.bounded_policy, nullptr, picks_.data(),
                                                  scores_.data(), nullptr)
@@ -929,6 +951,7 @@ class Scheduler {  // interface.go:55-66
   std::vector<int32_t> picks_;
   std::vector<double> scores_;
   std::vector<uint64_t> fmask_;
+  std::vector<uint8_t> bands_;
 };
 
 }  // namespace eppk_host

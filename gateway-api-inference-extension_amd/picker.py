@@ -214,6 +214,26 @@ def _bounded_caps(n_pods: int, cap, load):
     return cap_arr, cap_all, load
 
 
+def _band_table(bands) -> "_lib.BandTable":
+    """eppk_band_table of a sequence of (policy, reserve), band 0 first.  A sequence the table cannot hold (none, or more than
+    EPPK_MAX_BANDS) is handed over as its length alone, for the library to refuse."""
+    bands = list(bands)
+    t = _lib.BandTable()
+    t.n_bands = len(bands)
+    for b, (policy, reserve) in enumerate(bands[:_lib.EPPK_MAX_BANDS]):
+        t.policy[b], t.reserve[b] = int(policy) & 0xFFFFFFFF, int(reserve)
+    return t
+
+
+def _band_bytes(band, n_reqs: int):
+    """The band byte per request as a u8 array, or None (every request in band 0)."""
+    if band is None:
+        return None
+    band = np.ascontiguousarray(band, dtype=np.uint8)
+    assert band.shape == (n_reqs,), "one band byte per request"
+    return band
+
+
 class RoundRobinPicker:
     """server.go:84-101 — the reference's picker; the shim's fail-open fallback."""
 
@@ -607,6 +627,46 @@ class BatchedPicker:
                                                           int(policy), d_load or None, d_pick, d_score or None, d_rank or None, stream or None),
                     "bounded_resolve_device")
 
+    # -- ... with priority bands (SEMANTICS.md §3e) --------------------------------------------------
+    def pick_bounded_banded(self, reqs: np.ndarray, k: int, cap, bands, band: Optional[np.ndarray] = None, load: Optional[np.ndarray] = None,
+                            mask: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray]]:
+        """eppk_pick_banded: pick_bounded band by band.  `bands`: a sequence of (policy, reserve), band 0 (the most important) first;
+        `band`: a u8 per request (None: all in band 0).  Returns what pick_bounded returns."""
+        reqs = np.ascontiguousarray(reqs, dtype=np.uint64)
+        assert reqs.ndim == 2 and reqs.shape[1] == self.row_words, "request row stride mismatch"
+        R = reqs.shape[0]
+        mptr = None
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint64)
+            assert mask.shape == (R, (self.n_pods + 63) // 64), "mask shape mismatch"
+            mptr = mask.ctypes.data
+        cap_arr, cap_all, load = _bounded_caps(self.n_pods, cap, load)
+        band = _band_bytes(band, R)
+        picks = np.full(R, -1, dtype=np.int32)
+        scores = np.zeros(R, dtype=np.float64)
+        ranks = np.full(R, _lib.EPPK_RANK_NONE, dtype=np.uint8)
+        self._check(self._lib.eppk_pick_banded(self._ctx, reqs.ctypes.data, R, mptr, int(k), band.ctypes.data if band is not None else None,
+                                               C.byref(_band_table(bands)), cap_arr.ctypes.data if cap_arr is not None else None, cap_all,
+                                               load.ctypes.data if load is not None else None, picks.ctypes.data, scores.ctypes.data,
+                                               ranks.ctypes.data), "pick_bounded_banded")
+        return picks, scores, ranks, load
+
+    def pick_bounded_banded_device(self, d_reqs: int, n_reqs: int, d_mask: Optional[int], k: int, d_band: Optional[int], bands, d_cap: Optional[int],
+                                   cap_all: int, d_load: Optional[int], d_pick: int, d_score: Optional[int], d_rank: Optional[int],
+                                   stream: int = 0) -> None:
+        """eppk_pick_banded_device: device pointers as ints (d_band: n_reqs u8 or None), asynchronous on `stream`."""
+        self._check(self._lib.eppk_pick_banded_device(self._ctx, d_reqs, n_reqs, d_mask or None, int(k), d_band or None, C.byref(_band_table(bands)),
+                                                      d_cap or None, int(cap_all), d_load or None, d_pick, d_score or None, d_rank or None,
+                                                      stream or None), "pick_bounded_banded_device")
+
+    def bounded_resolve_banded_device(self, d_lists: int, d_list_scores: Optional[int], n_reqs: int, k: int, d_band: Optional[int], bands,
+                                      d_cap: Optional[int], cap_all: int, d_load: Optional[int], d_pick: int, d_score: Optional[int],
+                                      d_rank: Optional[int], stream: int = 0) -> None:
+        """eppk_banded_resolve_device: the banded resolve alone, over any [n_reqs][k] lists on the device."""
+        self._check(self._lib.eppk_banded_resolve_device(self._ctx, d_lists, d_list_scores or None, n_reqs, int(k), d_band or None,
+                                                         C.byref(_band_table(bands)), d_cap or None, int(cap_all), d_load or None, d_pick,
+                                                         d_score or None, d_rank or None, stream or None), "bounded_resolve_banded_device")
+
     def bounded_geometry(self) -> Tuple[int, int]:
         """(rows per chunk, the largest batch the one-launch kernel takes) of the bounded resolve (EPPK_BOUND_CHUNK)."""
         out = (C.c_uint32 * 2)()
@@ -889,6 +949,22 @@ class DeviceGroup:
         self._check(self._lib.eppk_group_pick_bounded(self._g, reqs.ctypes.data, R, mptr, int(k), cap_arr.ctypes.data if cap_arr is not None else None,
                                                       cap_all, int(policy), load.ctypes.data if load is not None else None, picks.ctypes.data,
                                                       scores.ctypes.data, ranks.ctypes.data), "group_pick_bounded")
+        return picks, scores, ranks, load
+
+    def pick_bounded_banded(self, reqs: np.ndarray, k: int, cap, bands, band: Optional[np.ndarray] = None, load: Optional[np.ndarray] = None,
+                            mask: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray]]:
+        """eppk_group_pick_banded: BatchedPicker.pick_bounded_banded over the group."""
+        reqs, mask, mptr = self._rows_and_mask(reqs, mask)
+        R = reqs.shape[0]
+        cap_arr, cap_all, load = _bounded_caps(self.n_pods, cap, load)
+        band = _band_bytes(band, R)
+        picks = np.full(R, -1, dtype=np.int32)
+        scores = np.zeros(R, dtype=np.float64)
+        ranks = np.full(R, _lib.EPPK_RANK_NONE, dtype=np.uint8)
+        self._check(self._lib.eppk_group_pick_banded(self._g, reqs.ctypes.data, R, mptr, int(k), band.ctypes.data if band is not None else None,
+                                                     C.byref(_band_table(bands)), cap_arr.ctypes.data if cap_arr is not None else None, cap_all,
+                                                     load.ctypes.data if load is not None else None, picks.ctypes.data, scores.ctypes.data,
+                                                     ranks.ctypes.data), "group_pick_bounded_banded")
         return picks, scores, ranks, load
 
     # -- the pipelined host path over the group (eppk_group_pick_stage_*) ---------------------------------------------

@@ -588,6 +588,50 @@ int eppk_group_pick_bounded(eppk_group* g, const void* reqs, uint32_t n_reqs, co
 /* Diagnostic: out = {rows per chunk, the largest n_reqs the one-launch kernel takes}. */
 int eppk_bounded_geometry(const eppk_ctx* ctx, uint32_t out[2]);
 
+/* ---- ... with priority bands (SEMANTICS.md §3e) -------------------------------------------------------------------------------
+ * The bounded picker sheds in batch order: a sheddable request in row 0 takes the last slot of a pod and the critical request in
+ * row 1 is refused.  The reference's API ranks requests by criticality ("Critical ... Requests to this band will be shed last",
+ * "Sheddable ... will be shed before", docs/proposals/002-api-proposal; an integer "with inherent stack rank",
+ * docs/proposals/1199-inferencemodel-api-evolution; the 429 of a dropped Sheddable request, docs/proposals/004-endpoint-picker-protocol).
+ * Here every request carries a BAND byte, band 0 the most important, and a table gives each band a policy and a RESERVE: the slots
+ * of EVERY pod the band may not use, cap_b[p] = cap[p] - min(cap[p], reserve_b).  For b = 0 .. n_bands - 1 in order, the requests of
+ * band b, in batch order, go through the whole resolve above (its k rounds, then what no round placed under policy_b) with cap_b, on
+ * the loads band b - 1 left.  Inside a band nothing changes; across bands priority is strict: no request of band b + 1 takes room a
+ * request of band b bids for in any of its rounds.  n_bands = 1 with reserve 0 is the resolve above bit for bit.  A load that a spill
+ * carries past 2^32 - 1 wraps in what is handed back, and the pod has no room for the bands behind.  The result is a pure function of
+ * the arguments.
+ *   d_band        nullable [n_reqs] u8; NULL: every request is in band 0.  A byte >= n_bands: on the *_device forms the request takes no
+ *                 room, gets EPPK_NO_PICK / 0.0 / EPPK_RANK_NONE and raises EPPK_LAUNCH_BAD_REQUEST_ROW (its list is still checked for
+ *                 EPPK_LAUNCH_BAD_PICK); the host-buffer forms refuse the batch with EPPK_ERR_ARG and name the lowest such row.
+ *   bands         HOST memory, read at the call: n_bands (1 .. EPPK_MAX_BANDS) entries; reserve must not decrease from band to band
+ *   every other argument as for the entry points above.
+ * The same notes hold: asynchronous on `stream`; ONE stream at a time per context for the bounded and banded entry points; the scratch
+ * (as above, and for a batch of more than one chunk a permutation, band histograms and segment bounds) grows on demand, and a call
+ * that has to grow it drains the DEVICE first, is not asynchronous and cannot be captured into a graph.  A batch of at most one
+ * chunk takes a single launch; a larger one is put in band order first (three launches: a stable permutation, the lists are not
+ * copied), then takes three launches per band and round -- the band's rows are found on the device, the *_device forms never wait
+ * for the host -- and one more.  The host-buffer forms skip the launches of a band without requests.  Errors: as above, and
+ * EPPK_ERR_ARG for a null table, n_bands outside 1 .. EPPK_MAX_BANDS, an unknown policy in a used entry, and decreasing reserves. */
+#define EPPK_MAX_BANDS 8u
+typedef struct eppk_band_table {
+  uint32_t n_bands;
+  uint32_t policy[EPPK_MAX_BANDS];     /* EPPK_BOUNDED_SHED / EPPK_BOUNDED_SPILL */
+  uint32_t reserve[EPPK_MAX_BANDS];    /* slots of every pod the band may not use */
+} eppk_band_table;
+int eppk_banded_resolve_device(eppk_ctx* ctx, const int32_t* d_lists, const double* d_list_scores, uint32_t n_reqs, uint32_t k,
+                               const uint8_t* d_band, const eppk_band_table* bands, const uint32_t* d_cap, uint32_t cap_all,
+                               uint32_t* d_load, int32_t* d_out_pick, double* d_out_score, uint8_t* d_out_rank, void* stream);
+int eppk_pick_banded_device(eppk_ctx* ctx, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, uint32_t k,
+                            const uint8_t* d_band, const eppk_band_table* bands, const uint32_t* d_cap, uint32_t cap_all,
+                            uint32_t* d_load, int32_t* d_out_pick, double* d_out_score, uint8_t* d_out_rank, void* stream);
+int eppk_pick_banded(eppk_ctx* ctx, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint8_t* band,
+                     const eppk_band_table* bands, const uint32_t* cap, uint32_t cap_all, uint32_t* load, int32_t* out_pick,
+                     double* out_score, uint8_t* out_rank);
+/* Over a group, as eppk_group_pick_bounded: member 0 resolves; equals eppk_pick_banded on the unsharded batch bit for bit. */
+int eppk_group_pick_banded(eppk_group* g, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k,
+                           const uint8_t* band, const eppk_band_table* bands, const uint32_t* cap, uint32_t cap_all, uint32_t* load,
+                           int32_t* out_pick, double* out_score, uint8_t* out_rank);
+
 /* ---- adjacent host-side steps of the same path ---------------------------------------------- */
 
 /* Chain-hash a prompt into block hashes (0602-…/README.md:99): XXH64, seed 0,
