@@ -11,6 +11,7 @@
 #include "eppk_filter.hip.h"
 #include "eppk_bounded.hip.h"
 #include "eppk_banded.hip.h"
+#include "eppk_costed.hip.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -207,6 +208,9 @@ struct eppk_ctx {
   uint32_t* d_bn_perm = nullptr; size_t bn_perm_rows = 0;   // place in the band order -> request
   uint32_t* d_bn_bh = nullptr; size_t bn_bh_words = 0;      // seg[0 .. 8] (kBandSegWords words), then [chunks][8] rows per band / their offsets
   uint8_t* d_bn_band = nullptr; size_t bn_band_rows = 0;    // band bytes of the host forms
+  // ... in cost units (SEMANTICS.md §3f; eppk_costed.hip.h)
+  uint32_t* d_cs_acc = nullptr; size_t cs_acc_words = 0;    // [EPPK_MAX_PODS] takers' totals of a round, until the next scan pass folds them into the load
+  uint32_t* d_cs_cost = nullptr; size_t cs_cost_rows = 0;   // costs of the host forms (per request)
 
   // measurement
   bool prof = false;
@@ -1508,6 +1512,7 @@ void eppk_destroy(eppk_ctx* c) {
   (void)hipFree(c->d_bd_hist); (void)hipFree(c->d_bd_state); (void)hipFree(c->d_bd_pods); (void)hipFree(c->d_bd_list); (void)hipFree(c->d_bd_lscore);
   (void)hipFree(c->d_bd_opick); (void)hipFree(c->d_bd_oscore); (void)hipFree(c->d_bd_orank);
   (void)hipFree(c->d_bn_perm); (void)hipFree(c->d_bn_bh); (void)hipFree(c->d_bn_band);
+  (void)hipFree(c->d_cs_acc); (void)hipFree(c->d_cs_cost);
   (void)hipFree(c->d_rows); (void)hipFree(c->d_rm); (void)hipFree(c->d_rs_pick); (void)hipFree(c->d_rs_score); (void)hipFree(c->d_learn);
   if (c->h_reqs) (void)hipHostFree(c->h_reqs);
   if (c->h_mask) (void)hipHostFree(c->h_mask);
@@ -3309,6 +3314,168 @@ int eppk_pick_banded(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint6
   return banded_host_finish(c, c->d_tk_pick, c->d_tk_score, n_reqs, k, band, counts, tab, cap, cap_all, load, out_pick, out_score, out_rank);
 }
 
+// ---- ... in cost units (SEMANTICS.md §3f; eppk_costed.hip.h) -------------------------------------------------------------------
+
+namespace {
+
+int costed_check(eppk_ctx* c, const char* who, uint32_t k, const eppk_band_table* t, const void* cost, uint32_t cost_flags, uint32_t n_reqs,
+                 eppk::BandTab* tab) {
+  const int rc = banded_check(c, who, k, t, tab);
+  if (rc) return rc;
+  if (cost_flags & ~EPPK_COST_PER_ENTRY) return fail(c, EPPK_ERR_ARG, std::string(who) + ": unknown cost flags " + std::to_string(cost_flags));
+  if (!cost && n_reqs) return fail(c, EPPK_ERR_ARG, std::string(who) + ": null cost (a caller without costs has the banded entry points)");
+  return EPPK_OK;
+}
+
+// Band bytes and costs of a host form, before anything is launched: the lowest bad row is named; the rows per band are counted.
+int costed_host_counts(eppk_ctx* c, const char* who, const uint8_t* band, const uint32_t* cost, uint32_t n_reqs, uint32_t n_bands,
+                       uint32_t counts[EPPK_MAX_BANDS]) {
+  for (uint32_t b = 0; b < EPPK_MAX_BANDS; ++b) counts[b] = 0u;
+  for (uint32_t r = 0; r < n_reqs; ++r) {
+    const uint32_t b = band ? band[r] : 0u;
+    if (b >= n_bands)
+      return fail(c, EPPK_ERR_ARG, std::string(who) + ": request row " + std::to_string(r) + " names band " + std::to_string(b) + " of " + std::to_string(n_bands));
+    if (cost[r] - 1u >= EPPK_MAX_COST)
+      return fail(c, EPPK_ERR_ARG, std::string(who) + ": request row " + std::to_string(r) + " has cost " + std::to_string(cost[r]) + " (1.." +
+                                       std::to_string(EPPK_MAX_COST) + ")");
+    ++counts[b];
+  }
+  return EPPK_OK;
+}
+
+// The launches of the costed resolve on `st` (arguments checked by the caller; n_reqs != 0).  `counts` as for banded_resolve.
+int costed_resolve(eppk_ctx* c, const int32_t* d_lists, const double* d_scores, uint32_t n_reqs, uint32_t k, const uint32_t* d_cost, uint32_t cost_flags,
+                   const uint8_t* d_band, const eppk::BandTab& tab, const uint32_t* counts, const uint32_t* d_cap, uint32_t cap_all, uint32_t* d_load,
+                   int32_t* d_out_pick, double* d_out_score, uint8_t* d_out_rank, hipStream_t st) {
+  const uint32_t P = c->n_pods, chunk = c->bound_chunk;
+  const eppk::CostOf cost{d_cost, k, cost_flags & EPPK_COST_PER_ENTRY};
+  uint8_t* state = d_out_rank;
+  if (!state) {
+    const int rc = bounded_grow(c, &c->bd_state_rows, bounded_rows(c, n_reqs), {{(void**)&c->d_bd_state, 1u}});
+    if (rc) return rc;
+    state = c->d_bd_state;
+  }
+  if (n_reqs <= chunk) {
+    hipLaunchKernelGGL(eppk::costed_resolve_one_kernel, dim3(1), dim3(eppk::kBoundThreads), 0, st, d_lists, d_scores, n_reqs, k, P, cost, d_band, tab, d_cap,
+                       cap_all, d_load, d_out_pick, d_out_score, state, c->d_status);
+    HIPCHK(c, hipGetLastError());
+    return EPPK_OK;
+  }
+  const uint32_t n_chunks = (uint32_t)(((uint64_t)n_reqs + chunk - 1u) / chunk);
+  int rc = bounded_pod_scratch(c);
+  if (rc) return rc;
+  if ((rc = bounded_grow(c, &c->bd_hist_words, (size_t)n_chunks * P, {{(void**)&c->d_bd_hist, sizeof(uint32_t)}}))) return rc;
+  if ((rc = bounded_grow(c, &c->bn_perm_rows, bounded_rows(c, n_reqs), {{(void**)&c->d_bn_perm, sizeof(uint32_t)}}))) return rc;
+  if ((rc = bounded_grow(c, &c->bn_bh_words, eppk::kBandSegWords + (size_t)n_chunks * EPPK_MAX_BANDS, {{(void**)&c->d_bn_bh, sizeof(uint32_t)}}))) return rc;
+  if ((rc = bounded_grow(c, &c->cs_acc_words, (size_t)EPPK_MAX_PODS, {{(void**)&c->d_cs_acc, sizeof(uint32_t)}}))) return rc;
+  uint32_t* seg = c->d_bn_bh;
+  uint32_t* bh = c->d_bn_bh + eppk::kBandSegWords;
+  uint32_t* perm = c->d_bn_perm;
+  uint32_t* room = c->d_bd_pods;
+  uint32_t* acc = c->d_cs_acc;
+  uint32_t* load = d_load;
+  if (!load) {
+    load = c->d_bd_pods + EPPK_MAX_PODS;
+    HIPCHK(c, hipMemsetAsync(load, 0, (size_t)EPPK_MAX_PODS * sizeof(uint32_t), st));
+  }
+  HIPCHK(c, hipMemsetAsync(acc, 0, (size_t)EPPK_MAX_PODS * sizeof(uint32_t), st));
+  HIPCHK(c, hipMemsetAsync(state, (int)eppk::kBoundUnassigned, n_reqs, st));
+  // grid-stride loops as wide as the CUs this context may use (EPPK_MAX_CU): the results do not depend on the width
+  const uint32_t wide = (uint32_t)c->num_cu * 4u;
+  const uint32_t chunk_grid = n_chunks < wide ? n_chunks : wide;
+  const uint32_t pod_wgs = (P + eppk::kBoundScanPods - 1u) / eppk::kBoundScanPods, pod_grid = pod_wgs < wide ? pod_wgs : wide;
+  const uint32_t row_wgs = (uint32_t)(((uint64_t)n_reqs + eppk::kBoundThreads - 1u) / eppk::kBoundThreads), row_grid = row_wgs < wide * 2u ? row_wgs : wide * 2u;
+  hipLaunchKernelGGL(eppk::banded_hist_kernel, dim3(chunk_grid), dim3(eppk::kBoundThreads), 0, st, d_band, n_reqs, tab.n_bands, chunk, n_chunks, bh);
+  hipLaunchKernelGGL(eppk::banded_offsets_kernel, dim3(1), dim3(eppk::kBoundThreads), 0, st, bh, n_chunks, seg);
+  hipLaunchKernelGGL(eppk::banded_scatter_kernel, dim3(chunk_grid), dim3(64), 0, st, d_band, n_reqs, tab.n_bands, chunk, n_chunks, (const uint32_t*)bh, perm);
+  if (P) for (uint32_t b = 0; b < tab.n_bands; ++b) {
+    uint32_t band_grid = chunk_grid;
+    if (counts) {
+      if (!counts[b]) continue;
+      const uint32_t band_chunks = (uint32_t)(((uint64_t)counts[b] + chunk - 1u) / chunk);
+      band_grid = band_chunks < wide ? band_chunks : wide;
+    }
+    const eppk::CostRoomGlobal room_now{d_cap, cap_all, tab.reserve[b], load, acc};
+    for (uint32_t j = 0; j < k; ++j) {
+      hipLaunchKernelGGL(eppk::costed_count_kernel, dim3(band_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, k, j, P, chunk, (const uint32_t*)seg, b,
+                         (const uint32_t*)perm, cost, room_now, state, c->d_bd_hist);
+      hipLaunchKernelGGL(eppk::costed_scan_kernel, dim3(pod_grid), dim3(eppk::kBoundScanSegs * eppk::kBoundScanPods), 0, st, c->d_bd_hist, chunk,
+                         (const uint32_t*)seg, b, P, d_cap, cap_all, tab.reserve[b], load, acc, room);
+      hipLaunchKernelGGL(eppk::costed_assign_kernel, dim3(band_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, d_scores, k, j, P, chunk, (const uint32_t*)seg,
+                         b, (const uint32_t*)perm, cost, (const uint32_t*)c->d_bd_hist, (const uint32_t*)room, acc, state, d_out_pick, d_out_score);
+    }
+  }
+  hipLaunchKernelGGL(eppk::costed_finish_kernel, dim3(row_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, d_scores, n_reqs, k, P, cost, d_band, tab.n_bands,
+                     tab.spill, load, (const uint32_t*)acc, state, d_out_pick, d_out_score, c->d_status);
+  HIPCHK(c, hipGetLastError());
+  return EPPK_OK;
+}
+
+// Band bytes and costs up (checked and counted by costed_host_counts), then as bounded_host_finish.
+int costed_host_finish(eppk_ctx* c, const int32_t* d_lists, const double* d_scores, uint32_t n_reqs, uint32_t k, const uint32_t* cost, const uint8_t* band,
+                       const uint32_t* counts, const eppk::BandTab& tab, const uint32_t* cap, uint32_t cap_all, uint32_t* load, int32_t* out_pick,
+                       double* out_score, uint8_t* out_rank) {
+  int rc;
+  if (band) {
+    if ((rc = bounded_grow(c, &c->bn_band_rows, bounded_rows(c, n_reqs), {{(void**)&c->d_bn_band, 1u}}))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_bn_band, band, n_reqs, hipMemcpyHostToDevice, c->stream));
+  }
+  if ((rc = bounded_grow(c, &c->cs_cost_rows, bounded_rows(c, n_reqs), {{(void**)&c->d_cs_cost, sizeof(uint32_t)}}))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->d_cs_cost, cost, (size_t)n_reqs * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  return bounded_host_around(c, n_reqs, cap, load, out_pick, out_score, out_rank,
+                             [&](const uint32_t* d_cap, uint32_t* d_load, int32_t* d_pick, double* d_score, uint8_t* d_rank) {
+                               return costed_resolve(c, d_lists, d_scores, n_reqs, k, c->d_cs_cost, 0u, band ? c->d_bn_band : nullptr, tab, counts, d_cap,
+                                                     cap_all, d_load, d_pick, d_score, d_rank, c->stream);
+                             });
+}
+
+}  // namespace
+
+int eppk_costed_resolve_device(eppk_ctx* c, const int32_t* d_lists, const double* d_list_scores, uint32_t n_reqs, uint32_t k, const uint32_t* d_cost,
+                               uint32_t cost_flags, const uint8_t* d_band, const eppk_band_table* bands, const uint32_t* d_cap, uint32_t cap_all,
+                               uint32_t* d_load, int32_t* d_out_pick, double* d_out_score, uint8_t* d_out_rank, void* stream) {
+  if (!c || ((!d_lists || !d_out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_costed_resolve_device: null argument");
+  eppk::BandTab tab;
+  const int rcc = costed_check(c, "eppk_costed_resolve_device", k, bands, d_cost, cost_flags, n_reqs, &tab);
+  if (rcc) return rcc;
+  if (n_reqs == 0) return EPPK_OK;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  return costed_resolve(c, d_lists, d_list_scores, n_reqs, k, d_cost, cost_flags, d_band, tab, nullptr, d_cap, cap_all, d_load, d_out_pick, d_out_score,
+                        d_out_rank, stream ? (hipStream_t)stream : c->stream);
+}
+
+int eppk_pick_costed_device(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, uint32_t k, const uint32_t* d_cost,
+                            const uint8_t* d_band, const eppk_band_table* bands, const uint32_t* d_cap, uint32_t cap_all, uint32_t* d_load,
+                            int32_t* d_out_pick, double* d_out_score, uint8_t* d_out_rank, void* stream) {
+  if (!c || ((!d_reqs || !d_out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_costed_device: null argument");
+  eppk::BandTab tab;
+  int rc = costed_check(c, "eppk_pick_costed_device", k, bands, d_cost, 0u, n_reqs, &tab);
+  if (rc) return rc;
+  if (n_reqs == 0) return EPPK_OK;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if ((rc = bounded_lists(c, n_reqs))) return rc;
+  if ((rc = eppk_pick_topk_device(c, d_reqs, n_reqs, d_cand_mask, k, c->d_bd_list, c->d_bd_lscore, stream))) return rc;
+  return costed_resolve(c, c->d_bd_list, c->d_bd_lscore, n_reqs, k, d_cost, 0u, d_band, tab, nullptr, d_cap, cap_all, d_load, d_out_pick, d_out_score,
+                        d_out_rank, stream ? (hipStream_t)stream : c->stream);
+}
+
+int eppk_pick_costed(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint32_t* cost, const uint8_t* band,
+                     const eppk_band_table* bands, const uint32_t* cap, uint32_t cap_all, uint32_t* load, int32_t* out_pick, double* out_score,
+                     uint8_t* out_rank) {
+  if (!c || ((!reqs || !out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_costed: null argument");
+  eppk::BandTab tab;
+  int rc = costed_check(c, "eppk_pick_costed", k, bands, cost, 0u, n_reqs, &tab);
+  if (rc) return rc;
+  if (n_reqs > c->cfg.max_batch) return fail(c, EPPK_ERR_LIMIT, "eppk_pick_costed: n_reqs > max_batch");
+  if (n_reqs == 0) return EPPK_OK;
+  if ((rc = validate_rows(c, "eppk_pick_costed", reqs, n_reqs))) return rc;
+  uint32_t counts[EPPK_MAX_BANDS];
+  if ((rc = costed_host_counts(c, "eppk_pick_costed", band, cost, n_reqs, tab.n_bands, counts))) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if ((rc = bounded_host_lists(c, reqs, n_reqs, cand_mask, k))) return rc;
+  return costed_host_finish(c, c->d_tk_pick, c->d_tk_score, n_reqs, k, cost, band, counts, tab, cap, cap_all, load, out_pick, out_score, out_rank);
+}
+
 // ---- on-device prompt hashing ------------------------------------------------------------------------
 
 int eppk_hash_prompts_device(eppk_ctx* c, const void* d_prompts, uint64_t prompt_stride, const uint32_t* d_prompt_len,
@@ -3975,6 +4142,32 @@ int eppk_group_pick_banded(eppk_group* g, const void* reqs, uint32_t n_reqs, con
     return gfail(g, EPPK_ERR_DEVICE, "eppk_group_pick_banded: upload failed");
   if ((rc = banded_host_finish(c0, c0->d_bd_list, c0->d_bd_lscore, n_reqs, k, band, counts, tab, cap, cap_all, load, out_pick,
                                out_score, out_rank)))
+    return mfail(rc);
+  return EPPK_OK;
+}
+
+int eppk_group_pick_costed(eppk_group* g, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint32_t* cost, const uint8_t* band,
+                           const eppk_band_table* bands, const uint32_t* cap, uint32_t cap_all, uint32_t* load, int32_t* out_pick, double* out_score,
+                           uint8_t* out_rank) {
+  if (!g || ((!reqs || !out_pick) && n_reqs)) return gfail(g, EPPK_ERR_ARG, "eppk_group_pick_costed: null argument");
+  eppk_ctx* c0 = g->ctx[0];
+  eppk::BandTab tab;
+  uint32_t counts[EPPK_MAX_BANDS];
+  int rc = costed_check(c0, "eppk_group_pick_costed", k, bands, cost, 0u, n_reqs, &tab);
+  if (!rc) rc = costed_host_counts(c0, "eppk_group_pick_costed", band, cost, n_reqs, tab.n_bands, counts);
+  if (rc) return gfail(g, rc, eppk_last_error(c0));
+  // as eppk_group_pick_bounded: the lists of the whole batch on the host, then ONE resolve on member 0
+  std::vector<int32_t> lists((size_t)n_reqs * k);
+  std::vector<double> totals((size_t)n_reqs * k);
+  if ((rc = group_topk(g, "eppk_group_pick_costed", reqs, n_reqs, cand_mask, k, false, 0ull, lists.data(), totals.data()))) return rc;
+  if (n_reqs == 0) return EPPK_OK;
+  auto mfail = [&](int code) { return gfail(g, code, "device " + std::to_string(g->dev[0]) + ": " + eppk_last_error(c0)); };
+  if (hipSetDevice(g->dev[0]) != hipSuccess) return gfail(g, EPPK_ERR_DEVICE, "eppk_group_pick_costed: hipSetDevice failed");
+  if ((rc = bounded_lists(c0, n_reqs))) return mfail(rc);
+  if (hipMemcpyAsync(c0->d_bd_list, lists.data(), lists.size() * 4u, hipMemcpyHostToDevice, c0->stream) != hipSuccess ||
+      hipMemcpyAsync(c0->d_bd_lscore, totals.data(), totals.size() * 8u, hipMemcpyHostToDevice, c0->stream) != hipSuccess)
+    return gfail(g, EPPK_ERR_DEVICE, "eppk_group_pick_costed: upload failed");
+  if ((rc = costed_host_finish(c0, c0->d_bd_list, c0->d_bd_lscore, n_reqs, k, cost, band, counts, tab, cap, cap_all, load, out_pick, out_score, out_rank)))
     return mfail(rc);
   return EPPK_OK;
 }

@@ -717,6 +717,8 @@ struct Request {  // interface.go:35-44
   std::string request_id, target_model, prompt;
   std::map<std::string, std::string> headers;
   uint8_t band = 0;                              // priority band, 0 = the most important (SEMANTICS.md §3e); read by a Bounded profile with bands
+  uint32_t cost = 1;                             // what the request takes of an endpoint's cap, 1 .. EPPK_MAX_COST (SEMANTICS.md §3f: prompt blocks);
+                                                 // read by a costed Bounded profile
 };
 
 struct ScoredEndpoint {  // interface.go:50-53
@@ -748,6 +750,8 @@ struct ProfileSpec {
   uint32_t bounded_policy = EPPK_BOUNDED_SHED;   // bounded: what becomes of a request that finds every entry full (SHED: Unavailable)
   std::vector<eppk_band> bands;                  // bounded: priority bands, band 0 first (SEMANTICS.md §3e); Request::band picks the entry, and
                                                  // bounded_policy is not read.  Empty = no bands: batch order alone decides (§3d)
+  bool costed = false;                           // bounded: cap_all and the reserves are in COST units and every request takes Request::cost of
+                                                 // them (SEMANTICS.md §3f; eppk_pick_costed).  Empty `bands` = one band with bounded_policy
   std::vector<eppk_predicate> predicates;        // metric predicates behind `filter` (SEMANTICS.md §2c): ONE program, evaluated on the device
                                                  // against the gauges of the snapshot; empty = none.  A request they shed gets Unavailable.
 };
@@ -799,6 +803,7 @@ class Scheduler {  // interface.go:55-66
       GpuPickerOptions go; go.max_pods = opt.max_pods; go.max_blocks = opt.max_blocks; go.max_batch = opt.max_batch;
       // (a cap of 0 leaves no room on any endpoint: every request would end as Unavailable -- a profile that forgot to set it)
       if (ps.picker == PickerKind::Bounded && ps.cap_all == 0) return {Code::Internal, std::string("profile ") + ps.name + ": the bounded picker needs cap_all > 0"};
+      if (ps.costed && ps.picker != PickerKind::Bounded) return {Code::Internal, std::string("profile ") + ps.name + ": costed needs the bounded picker"};
       if (ps.bands.size() > EPPK_MAX_BANDS) return {Code::Internal, std::string("profile ") + ps.name + ": more than 8 bands"};
       for (size_t b = 1; b < ps.bands.size(); ++b)
         if (ps.bands[b].reserve < ps.bands[b - 1].reserve)
@@ -847,11 +852,19 @@ class Scheduler {  // interface.go:55-66
     const size_t n = requests.size();
     std::vector<std::map<std::string, std::vector<ScoredEndpoint>>> results(n);
     const size_t stride = 8u + 8u * opt_.max_blocks;
+    std::vector<std::string> refused(n);              // a request a costed profile cannot take: its own Internal status, the batch goes on
     for (int round = 0; round < 16; ++round) {        // (a handler that never stops is cut off)
       std::map<std::string, std::vector<uint32_t>> group;
       for (size_t r = 0; r < n; ++r)
-        for (const std::string& name : handler_->Pick(requests[r], names_, results[r]))
-          if (!results[r].count(name)) group[name].push_back((uint32_t)r);
+        for (const std::string& name : handler_->Pick(requests[r], names_, results[r])) {
+          if (results[r].count(name)) continue;
+          if (requests[r].cost - 1u >= EPPK_MAX_COST && Costed(name)) {   // before the call: the library would refuse the whole batch
+            results[r][name];                                             // (the profile has run, without an endpoint)
+            refused[r] = "profile " + name + ": request cost " + std::to_string(requests[r].cost) + " out of range (1.." + std::to_string(EPPK_MAX_COST) + ")";
+            continue;
+          }
+          group[name].push_back((uint32_t)r);
+        }
       if (group.empty()) break;
       for (Prof& p : profiles_) {
         auto g = group.find(p.spec.name);
@@ -894,8 +907,18 @@ class Scheduler {  // interface.go:55-66
             if (eppk_filter_masks(p.ctx.get(), rows, m, nullptr, nullptr, fmask_.data(), nullptr) != EPPK_OK) return {Code::Internal, eppk_last_error(p.ctx.get())};
             fmask = fmask_.data();
           }
+          const bool costed = p.spec.picker == PickerKind::Bounded && p.spec.costed;
           const bool banded = p.spec.picker == PickerKind::Bounded && !p.spec.bands.empty();
           eppk_band_table table;
+          if (costed) {
+            costs_.resize(m);
+            for (uint32_t i = 0; i < m; ++i) costs_[i] = requests[idx[lo + i]].cost;
+            if (!banded) {                                             // one band with the profile's policy: the cost form of §3d
+              std::memset(&table, 0, sizeof table);
+              table.n_bands = 1u;
+              table.policy[0] = p.spec.bounded_policy;
+            }
+          }
           if (banded) {
             std::memset(&table, 0, sizeof table);
             table.n_bands = (uint32_t)p.spec.bands.size();
@@ -908,6 +931,9 @@ class Scheduler {  // interface.go:55-66
                              ? eppk_pick_filtered(p.ctx.get(), rows, m, nullptr, nullptr, 1, picks_.data(), scores_.data(), nullptr)
                          : p.spec.picker == PickerKind::BestScore
                              ? eppk_pick_batch(p.ctx.get(), rows, m, nullptr, picks_.data(), scores_.data())
+                         : costed
+                             ? eppk_pick_costed(p.ctx.get(), rows, m, fmask, p.spec.k, costs_.data(), banded ? bands_.data() : nullptr, &table, nullptr,
+                                                p.spec.cap_all, nullptr, picks_.data(), scores_.data(), nullptr)
                          : banded
                              ? eppk_pick_banded(p.ctx.get(), rows, m, fmask, p.spec.k, bands_.data(), &table, nullptr, p.spec.cap_all, nullptr, picks_.data(),
                                                 scores_.data(), nullptr)
@@ -930,6 +956,7 @@ class Scheduler {  // interface.go:55-66
       (*out)[r] = handler_->ProcessResults(requests[r], results[r]);
       auto pr = (*out)[r].profile_results.find((*out)[r].primary_profile_name);
       if (pr == (*out)[r].profile_results.end() || pr->second.empty()) (*statuses)[r] = {Code::Unavailable, "no endpoints available"};
+      if (!refused[r].empty()) (*statuses)[r] = {Code::Internal, refused[r]};
     }
     return {};
   }
@@ -941,6 +968,10 @@ class Scheduler {  // interface.go:55-66
 
  private:
   struct Prof { ProfileSpec spec; std::shared_ptr<eppk_ctx> ctx; };
+  bool Costed(const std::string& profile) const {
+    for (const Prof& p : profiles_) if (p.spec.name == profile) return p.spec.costed;
+    return false;
+  }
   Options opt_;
   ProfileHandler* handler_ = nullptr;
   std::vector<Prof> profiles_;
@@ -952,6 +983,7 @@ class Scheduler {  // interface.go:55-66
   std::vector<double> scores_;
   std::vector<uint64_t> fmask_;
   std::vector<uint8_t> bands_;
+  std::vector<uint32_t> costs_;
 };
 
 }  // namespace eppk_host

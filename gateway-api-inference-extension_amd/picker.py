@@ -234,6 +234,17 @@ def _band_bytes(band, n_reqs: int):
     return band
 
 
+def _cost_words(cost, n_reqs: int):
+    """The cost per request as a u32 array (a value that does not fit 32 bits is refused here; the library checks the range)."""
+    if cost is None:
+        raise EppkError(-1, "costed pick: no costs (a caller without costs has pick_bounded_banded)")
+    a = np.asarray(cost)
+    assert a.shape == (n_reqs,), "one cost per request"
+    if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+        raise EppkError(-1, "costed pick: cost out of range (u32)")
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
 class RoundRobinPicker:
     """server.go:84-101 — the reference's picker; the shim's fail-open fallback."""
 
@@ -667,6 +678,50 @@ class BatchedPicker:
                                                          C.byref(_band_table(bands)), d_cap or None, int(cap_all), d_load or None, d_pick,
                                                          d_score or None, d_rank or None, stream or None), "bounded_resolve_banded_device")
 
+    # -- ... in cost units (SEMANTICS.md §3f) --------------------------------------------------------
+    def pick_bounded_costed(self, reqs: np.ndarray, k: int, cost, cap, bands=((_lib.EPPK_BOUNDED_SHED, 0),), band: Optional[np.ndarray] = None,
+                            load: Optional[np.ndarray] = None, mask: Optional[np.ndarray] = None
+                            ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray]]:
+        """eppk_pick_costed: pick_bounded_banded with a cost per request (u32 [R], 1 .. EPPK_MAX_COST); `cap`, `load` and the reserves
+        of `bands` are in cost units.  Returns what pick_bounded returns."""
+        reqs = np.ascontiguousarray(reqs, dtype=np.uint64)
+        assert reqs.ndim == 2 and reqs.shape[1] == self.row_words, "request row stride mismatch"
+        R = reqs.shape[0]
+        mptr = None
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint64)
+            assert mask.shape == (R, (self.n_pods + 63) // 64), "mask shape mismatch"
+            mptr = mask.ctypes.data
+        cap_arr, cap_all, load = _bounded_caps(self.n_pods, cap, load)
+        band = _band_bytes(band, R)
+        cost = _cost_words(cost, R)
+        picks = np.full(R, -1, dtype=np.int32)
+        scores = np.zeros(R, dtype=np.float64)
+        ranks = np.full(R, _lib.EPPK_RANK_NONE, dtype=np.uint8)
+        self._check(self._lib.eppk_pick_costed(self._ctx, reqs.ctypes.data, R, mptr, int(k), cost.ctypes.data,
+                                               band.ctypes.data if band is not None else None, C.byref(_band_table(bands)),
+                                               cap_arr.ctypes.data if cap_arr is not None else None, cap_all,
+                                               load.ctypes.data if load is not None else None, picks.ctypes.data, scores.ctypes.data,
+                                               ranks.ctypes.data), "pick_bounded_costed")
+        return picks, scores, ranks, load
+
+    def pick_bounded_costed_device(self, d_reqs: int, n_reqs: int, d_mask: Optional[int], k: int, d_cost: Optional[int], d_band: Optional[int], bands,
+                                   d_cap: Optional[int], cap_all: int, d_load: Optional[int], d_pick: int, d_score: Optional[int],
+                                   d_rank: Optional[int], stream: int = 0) -> None:
+        """eppk_pick_costed_device: device pointers as ints (d_cost: n_reqs u32), asynchronous on `stream`."""
+        self._check(self._lib.eppk_pick_costed_device(self._ctx, d_reqs, n_reqs, d_mask or None, int(k), d_cost or None, d_band or None,
+                                                      C.byref(_band_table(bands)), d_cap or None, int(cap_all), d_load or None, d_pick,
+                                                      d_score or None, d_rank or None, stream or None), "pick_bounded_costed_device")
+
+    def bounded_resolve_costed_device(self, d_lists: int, d_list_scores: Optional[int], n_reqs: int, k: int, d_cost: Optional[int], cost_flags: int,
+                                      d_band: Optional[int], bands, d_cap: Optional[int], cap_all: int, d_load: Optional[int], d_pick: int,
+                                      d_score: Optional[int], d_rank: Optional[int], stream: int = 0) -> None:
+        """eppk_costed_resolve_device: the costed resolve alone, over any [n_reqs][k] lists on the device; cost_flags
+        EPPK_COST_PER_ENTRY: d_cost is [n_reqs][k]."""
+        self._check(self._lib.eppk_costed_resolve_device(self._ctx, d_lists, d_list_scores or None, n_reqs, int(k), d_cost or None, int(cost_flags),
+                                                         d_band or None, C.byref(_band_table(bands)), d_cap or None, int(cap_all), d_load or None,
+                                                         d_pick, d_score or None, d_rank or None, stream or None), "bounded_resolve_costed_device")
+
     def bounded_geometry(self) -> Tuple[int, int]:
         """(rows per chunk, the largest batch the one-launch kernel takes) of the bounded resolve (EPPK_BOUND_CHUNK)."""
         out = (C.c_uint32 * 2)()
@@ -965,6 +1020,25 @@ class DeviceGroup:
                                                      C.byref(_band_table(bands)), cap_arr.ctypes.data if cap_arr is not None else None, cap_all,
                                                      load.ctypes.data if load is not None else None, picks.ctypes.data, scores.ctypes.data,
                                                      ranks.ctypes.data), "group_pick_bounded_banded")
+        return picks, scores, ranks, load
+
+    def pick_bounded_costed(self, reqs: np.ndarray, k: int, cost, cap, bands=((_lib.EPPK_BOUNDED_SHED, 0),), band: Optional[np.ndarray] = None,
+                            load: Optional[np.ndarray] = None, mask: Optional[np.ndarray] = None
+                            ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray]]:
+        """eppk_group_pick_costed: BatchedPicker.pick_bounded_costed over the group."""
+        reqs, mask, mptr = self._rows_and_mask(reqs, mask)
+        R = reqs.shape[0]
+        cap_arr, cap_all, load = _bounded_caps(self.n_pods, cap, load)
+        band = _band_bytes(band, R)
+        cost = _cost_words(cost, R)
+        picks = np.full(R, -1, dtype=np.int32)
+        scores = np.zeros(R, dtype=np.float64)
+        ranks = np.full(R, _lib.EPPK_RANK_NONE, dtype=np.uint8)
+        self._check(self._lib.eppk_group_pick_costed(self._g, reqs.ctypes.data, R, mptr, int(k), cost.ctypes.data,
+                                                     band.ctypes.data if band is not None else None, C.byref(_band_table(bands)),
+                                                     cap_arr.ctypes.data if cap_arr is not None else None, cap_all,
+                                                     load.ctypes.data if load is not None else None, picks.ctypes.data, scores.ctypes.data,
+                                                     ranks.ctypes.data), "group_pick_bounded_costed")
         return picks, scores, ranks, load
 
     # -- the pipelined host path over the group (eppk_group_pick_stage_*) ---------------------------------------------

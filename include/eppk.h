@@ -632,6 +632,52 @@ int eppk_group_pick_banded(eppk_group* g, const void* reqs, uint32_t n_reqs, con
                            const uint8_t* band, const eppk_band_table* bands, const uint32_t* cap, uint32_t cap_all, uint32_t* load,
                            int32_t* out_pick, double* out_score, uint8_t* out_rank);
 
+/* ---- ... in cost units (SEMANTICS.md §3f) -------------------------------------------------------------------------------------
+ * The entry points above count REQUESTS: a cap of 64 is 64 requests, a 12-token ping or a 100 000-token prompt alike.  The reference's
+ * scheduler proposal budgets cost instead: "Understand the cost of an incoming request and its impact on the target model server before
+ * placing it ... Track the cost of previously issued requests ... the cost of the request is the resources it will consume ... memory
+ * (as kv-cache)" (docs/proposals/006-scheduler/README.md:139-144; "Request Cost", :77-80).  Here every request carries a COST c,
+ * 1 <= c <= EPPK_MAX_COST, and cap, load and reserve are in the same units (cost = prompt blocks, cap = free KV blocks).
+ * For band b = 0 .. n_bands - 1 and round j = 0 .. k - 1 in order, with room[p] = max(cap_b[p] - load[p], 0) on the loads as the round
+ * before left them: a request of band b that is still unassigned and whose entry j is a valid pod p is a BIDDER of p iff c <= room[p]
+ * (one that could not fit even alone counts for nothing in this round and waits for its next entry: no head-of-line block); with S the
+ * sum of the costs of p's bidders in front of it in batch order, it gets p iff S + c <= room[p], and load[p] grows by the takers'
+ * total.  What no round placed is finished ONCE, behind the last band, with the policy of the request's own band: SHED as above; SPILL
+ * to the first valid entry, whose load grows by the request's cost (modulo 2^32 in what is handed back).  Under costs this is NOT a
+ * finish inside each band (a spilled large request leaves room a later band still uses; SEMANTICS.md §3f has the example).  All sums
+ * are exact; the result is a pure function of the arguments.  Every cost 1 is eppk_banded_resolve_device bit for bit.
+ *   d_cost        u32 [n_reqs], never NULL (a caller without costs has the entry points above); with EPPK_COST_PER_ENTRY in cost_flags
+ *                 u32 [n_reqs][k]: the cost of request r if it lands on entry j (a caller can charge only the uncached blocks).  A cost
+ *                 outside 1 .. EPPK_MAX_COST makes the row bad -- per request: checked for every row; per entry: only at positions
+ *                 whose list entry is a valid pod -- as a band byte >= n_bands does: on the *_device forms the row takes no room, gets
+ *                 EPPK_NO_PICK / 0.0 / EPPK_RANK_NONE and raises EPPK_LAUNCH_BAD_REQUEST_ROW (its list is still checked for
+ *                 EPPK_LAUNCH_BAD_PICK); the host-buffer forms refuse the batch with EPPK_ERR_ARG and name the lowest such row.
+ *   d_band NULL and a one-band table give the cost form of the plain bounded resolve.  Every other argument as above; the pick forms
+ *   take per-request costs only (the caller cannot know the lists).
+ * The same notes hold: asynchronous on `stream`; ONE stream at a time per context for the bounded, banded and costed entry points; the
+ * scratch (as above, and the takers' totals per pod) grows on demand, and a call that has to grow it drains the DEVICE first, is not
+ * asynchronous and cannot be captured into a graph.  A batch of at most one chunk takes a single launch; a larger one is put in band
+ * order first (three launches), then takes three launches per band and round -- the band's rows are found on the device, the *_device
+ * forms never wait for the host -- and one more.  Always launches (also under EPPK_RESIDENT=1).  Errors: as above, and EPPK_ERR_ARG
+ * for a null d_cost or an unknown bit in cost_flags. */
+#define EPPK_MAX_COST 0x00FFFFFFu
+#define EPPK_COST_PER_ENTRY 1u
+int eppk_costed_resolve_device(eppk_ctx* ctx, const int32_t* d_lists, const double* d_list_scores, uint32_t n_reqs, uint32_t k,
+                               const uint32_t* d_cost, uint32_t cost_flags, const uint8_t* d_band, const eppk_band_table* bands,
+                               const uint32_t* d_cap, uint32_t cap_all, uint32_t* d_load, int32_t* d_out_pick, double* d_out_score,
+                               uint8_t* d_out_rank, void* stream);
+int eppk_pick_costed_device(eppk_ctx* ctx, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, uint32_t k,
+                            const uint32_t* d_cost, const uint8_t* d_band, const eppk_band_table* bands, const uint32_t* d_cap,
+                            uint32_t cap_all, uint32_t* d_load, int32_t* d_out_pick, double* d_out_score, uint8_t* d_out_rank,
+                            void* stream);
+int eppk_pick_costed(eppk_ctx* ctx, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint32_t* cost,
+                     const uint8_t* band, const eppk_band_table* bands, const uint32_t* cap, uint32_t cap_all, uint32_t* load,
+                     int32_t* out_pick, double* out_score, uint8_t* out_rank);
+/* Over a group, as eppk_group_pick_banded: member 0 resolves; equals eppk_pick_costed on the unsharded batch bit for bit. */
+int eppk_group_pick_costed(eppk_group* g, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint32_t* cost,
+                           const uint8_t* band, const eppk_band_table* bands, const uint32_t* cap, uint32_t cap_all, uint32_t* load,
+                           int32_t* out_pick, double* out_score, uint8_t* out_rank);
+
 /* ---- adjacent host-side steps of the same path ---------------------------------------------- */
 
 /* Chain-hash a prompt into block hashes (0602-…/README.md:99): XXH64, seed 0,
