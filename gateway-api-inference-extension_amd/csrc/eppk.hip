@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../../include/eppk.h"
+#include "eppk_mem.hpp"
 
 using namespace eppk;
 
@@ -41,9 +42,24 @@ std::string g_create_err;
 std::mutex g_lds_mu;
 std::map<std::pair<int, const void*>, size_t> g_lds_limit;   // (device, kernel) -> dynamic-LDS limit set so far (occupancy_of)
 
+// The two memory policies of eppk_mem.hpp: the raw HIP memory calls appear here and nowhere else in this file.
+struct DeviceMem {
+  static int alloc(void** p, size_t bytes) { if (hipMalloc(p, bytes) == hipSuccess) return 0; (void)hipGetLastError(); return 1; }
+  static void release(void* p) { (void)hipFree(p); }
+  static int alias(void** dev, void* p) { *dev = p; return 0; }
+};
+template <unsigned Flags> struct PinnedMem {        // Flags: hipHostMallocDefault for a context, hipHostMallocPortable for a group
+  static int alloc(void** p, size_t bytes) { if (hipHostMalloc(p, bytes, Flags) == hipSuccess) return 0; (void)hipGetLastError(); return 1; }
+  static void release(void* p) { (void)hipHostFree(p); }
+  static int alias(void** dev, void* host) { if (hipHostGetDevicePointer(dev, host, 0) == hipSuccess) return 0; (void)hipGetLastError(); return 1; }
+};
+template <class T> using DBuf = eppk::Buf<T, DeviceMem>;
+template <class T> using HBuf = eppk::Buf<T, PinnedMem<hipHostMallocDefault>>;     // .dev(): the pinned buffer as the device addresses it
+template <class T> using GBuf = eppk::Buf<T, PinnedMem<hipHostMallocPortable>>;
+
 // One device allocation per snapshot buffer; the arrays below are views into it (fast kernel: one buffer descriptor).
 struct SnapBuf {
-  uint8_t*  blob = nullptr;
+  DBuf<uint8_t> blob;
   double*   base = nullptr;
   double*   post[2] = {nullptr, nullptr};   // products of the pod-only scorers behind LORA / PREFIX (GEN fast path)
   uint32_t* queue = nullptr;
@@ -86,7 +102,7 @@ struct eppk_ctx {
   KChain postc{};          // those scorers (n <= 2)
   KTail tail{};
   KChain kchain{};
-  double* pterm = nullptr;  // device [(B+1)*(B+1)] exact prefix terms (fast path, max_blocks <= 64)
+  DBuf<double> pterm;       // device [(B+1)*(B+1)] exact prefix terms (fast path, max_blocks <= 64)
   uint32_t pterm_ld = 0;
 
   // snapshot (double buffered: a publish never overwrites the rows an in-flight pick reads)
@@ -97,56 +113,54 @@ struct eppk_ctx {
   uint32_t n_pods = 0;
   uint64_t epoch = 0;
   uint32_t assumed_epochs = 0;     // SEMANTICS.md §2b (eppk_set_assumed_load); 0 = off
-  int32_t* d_rs_pick = nullptr; double* d_rs_score = nullptr; size_t rs_cap = 0;   // fallback lists of eppk_pick_random_topk
+  DBuf<int32_t> d_rs_pick; DBuf<double> d_rs_score;   // (capacity: entries) fallback lists of eppk_pick_random_topk
 
   // prefix index
   uint64_t* keys = nullptr;
-  void* bitmaps = nullptr;
+  DBuf<void> bitmaps;
   uint32_t slots = 0, shift = 0, limit = 0;
   size_t rows_bytes = 0, index_bytes = 0;   // rows | keys in one allocation
-  uint32_t* rstamps = nullptr;              // [2] exact stamps of the two reserved rows (hashes 0 / ~0: no bucket header); every other key's stamp is
+  DBuf<uint32_t> rstamps;                   // [2] exact stamps of the two reserved rows (hashes 0 / ~0: no bucket header); every other key's stamp is
                                             // a TAG in its bucket header (eppk_kernels.hip.h: "stamps as tags")
   uint32_t min_live = 0;                    // no live key is stamped before this epoch (the largest eviction horizon so far): the tags' window
-  uint32_t* lists = nullptr;                // [slots + 4][16] short pod lists: where a set with at most kListCap members lives (always maintained),
+  DBuf<uint32_t> lists;                     // [slots + 4][16] short pod lists: where a set with at most kListCap members lives (always maintained),
                                             // then the SET TABLE [sets_cap][16]: interned copies of the listed sets, named by the set ids in the bucket lines
   uint32_t sets_cap = 0;                    // lines of the set table (a power of two)
-  uint32_t* set_ctl = nullptr;              // device [2]: set-table lines in use, sets that found no line
-  uint32_t* h_set_report = nullptr;         // pinned [2]: the same two, as index_canon_kernel last left them (read without synchronising)
-  uint32_t* h_set_report_dev = nullptr;     // ([2] of the same pinned block: "a capacity verdict was bound by the words" -- index_budget_kernel and the resident LEARN
+  DBuf<uint32_t> set_ctl;                   // device [2]: set-table lines in use, sets that found no line
+  HBuf<uint32_t> h_set_report;              // pinned [2]: the same two, as index_canon_kernel last left them (read without synchronising)
+                                            // ([2] of the same pinned block: "a capacity verdict was bound by the words" -- index_budget_kernel and the resident LEARN
                                             //  prologue write it, the next eviction / trim / removal queues the reclaim pass behind itself: index_reclaim below)
-  uint32_t* d_crossed = nullptr;            // scratch of the reclaim pass: one bit per bucket (index updates of a context are ordered: one pass at a time)
+  DBuf<uint32_t> d_crossed;                 // scratch of the reclaim pass: one bit per bucket (index updates of a context are ordered: one pass at a time)
   uint32_t set_fail_seen = 0;               // sets without a line as of the last rebuild
   uint32_t set_passes = 0;                  // canon passes since the last rebuild (a table whose LIVE sets fill half of it is not rebuilt on every update)
   bool list_routes = true;                  // EPPK_LISTS=0: the pick kernels' list routes are off (every request takes the dense route)
-  uint32_t* sortwl = nullptr;               // work list of index_canon_kernel: cursors[2] | lost | arrived | slots[sortwl_cap]
-  uint32_t sortwl_cap = 0, sort_uses = 0;
-  eppk::IxLaunch* d_ixl = nullptr;          // the capacity verdict of the insert launch in flight (index_budget_kernel)
+  DBuf<uint32_t> sortwl;                    // work list of index_canon_kernel: cursors[2] | lost | arrived | slots[cap()] (capacity: slots)
+  uint32_t sort_uses = 0;
+  DBuf<eppk::IxLaunch> d_ixl;               // the capacity verdict of the insert launch in flight (index_budget_kernel)
   uint32_t index_epoch = 1;
-  unsigned long long* stats = nullptr;  // device [4 + kStatBanks*2*kStatSlots]: scratch, live keys, non-empty words, dropped inserts, then
+  DBuf<unsigned long long> stats;       // device [4 + kStatBanks*2*kStatSlots]: scratch, live keys, non-empty words, dropped inserts, then
                                         // banks of per-wave {hits, lookups}: consecutive launches use different banks, so pick
                                         // kernels overlapping on two streams never share a slot
   uint32_t stat_bank = 0;
-  uint32_t* d_status = nullptr;         // sticky launch-status flags (eppk_launch_status)
-  unsigned long long* ixc = nullptr;    // [kIxShards][8] sharded index counters: live keys, non-empty words, dropped inserts, evicted
+  DBuf<uint32_t> d_status;              // sticky launch-status flags (eppk_launch_status)
+  DBuf<unsigned long long> ixc;         // [kIxShards][8] sharded index counters: live keys, non-empty words, dropped inserts, evicted
 
   // subset filter on the device: fingerprints of the published endpoints (eppk_snapshot_set_addresses), entry staging
-  uint64_t* d_at = nullptr; uint32_t* d_av = nullptr; uint32_t at_slots = 0; bool have_addrs = false; uint32_t addr_n = 0;
-  uint64_t* d_sk = nullptr; uint32_t* d_so = nullptr; size_t sk_cap = 0, so_cap = 0;
+  DBuf<uint64_t> d_at; DBuf<uint32_t> d_av; uint32_t at_slots = 0; bool have_addrs = false; uint32_t addr_n = 0;
+  DBuf<uint64_t> d_sk; DBuf<uint32_t> d_so;      // (capacities: entries of 16 bytes; offsets)
 
   // staging for the host-buffer entry point
-  void* h_reqs = nullptr; uint64_t* h_mask = nullptr; int32_t* h_pick = nullptr; double* h_score = nullptr;
-  void* d_reqs = nullptr; uint64_t* d_mask = nullptr; int32_t* d_pick = nullptr; double* d_score = nullptr;
-  void* h_reqs_dev = nullptr; uint64_t* h_mask_dev = nullptr; int32_t* h_pick_dev = nullptr; double* h_score_dev = nullptr;   // the pinned buffers as the device addresses them
-  void* d_tmp = nullptr; size_t d_tmp_bytes = 0;  // index insert staging
+  HBuf<void> h_reqs; HBuf<uint64_t> h_mask; HBuf<int32_t> h_pick; HBuf<double> h_score;
+  DBuf<void> d_reqs; DBuf<uint64_t> d_mask; DBuf<int32_t> d_pick; DBuf<double> d_score;
+  DBuf<void> d_tmp;  // index insert staging (capacity: bytes)
   // the pipelined host path (eppk_pick_stage_*): per set its own pinned + device buffers, stream and events
   struct StageSet {
     hipStream_t st = nullptr; hipEvent_t picked = nullptr;
     hipStream_t st_copy = nullptr; hipEvent_t copied = nullptr; bool copy_pending = false;   // zero-copy pick + LEARN: the rows' device copy rides beside the pick
-    uint32_t* h_bad = nullptr; uint32_t* h_bad_dev = nullptr; hipStream_t st_check = nullptr; hipEvent_t checked = nullptr;   // device-side row check (eppk_ctx::RowCheck)
+    HBuf<uint32_t> h_bad; hipStream_t st_check = nullptr; hipEvent_t checked = nullptr;   // device-side row check (eppk_ctx::RowCheck)
     bool check_pending = false, check_side = false;
-    void* h_reqs = nullptr; uint64_t* h_mask = nullptr; int32_t* h_pick = nullptr; double* h_score = nullptr;
-    void* d_reqs = nullptr; uint64_t* d_mask = nullptr; int32_t* d_pick = nullptr; double* d_score = nullptr;
-    void* h_reqs_dev = nullptr; uint64_t* h_mask_dev = nullptr; int32_t* h_pick_dev = nullptr; double* h_score_dev = nullptr;
+    HBuf<void> h_reqs; HBuf<uint64_t> h_mask; HBuf<int32_t> h_pick; HBuf<double> h_score;
+    DBuf<void> d_reqs; DBuf<uint64_t> d_mask; DBuf<int32_t> d_pick; DBuf<double> d_score;
     uint32_t n = 0; bool busy = false, had_mask = false;
     uint32_t row_base = 0;       // a group member's set: batch index of the first row its device-side check looked at
     bool resident = false; uint32_t res_unit = 0, res_seq = 0;   // the batch between begin and end was rung into a resident workgroup (no launch)
@@ -169,48 +183,48 @@ struct eppk_ctx {
   hipStream_t res_slot_stream[kResSlots] = {nullptr, nullptr, nullptr, nullptr};   // high-priority streams: one hardware queue per running resident kernel
   int32_t res_slot_unit[kResSlots] = {-1, -1, -1, -1};                               // which unit runs on the slot (-1: free)
   uint64_t res_clock = 0;                                                            // LRU clock of the units (ResidentUnit::last_rung)
-  uint8_t* d_res_rows = nullptr; uint32_t* d_res_learn = nullptr; uint32_t* d_res_sortwl = nullptr;   // LEARN units: row copies, learn words, sort work lists (per unit)
+  DBuf<uint8_t> d_res_rows; DBuf<uint32_t> d_res_learn; DBuf<uint32_t> d_res_sortwl;   // LEARN units: row copies, learn words, sort work lists (per unit)
   struct ResidentUnit {
-    eppk::ResidentCtl* h_ctl = nullptr; eppk::ResidentCtl* h_ctl_dev = nullptr; hipStream_t stream = nullptr;
+    HBuf<eppk::ResidentCtl> h_ctl; hipStream_t stream = nullptr;
     bool running = false; uint32_t seq = 0;   // seq = the last doorbell value rung
     bool pending = false; uint32_t pending_seq = 0;   // a doorbell rung (eppk_pick_stage_begin) and not collected yet
     bool updating = false; uint32_t update_seq = 0;   // LEARN units: the index update behind that doorbell has not been seen finished yet
     int32_t slot = -1; uint64_t last_rung = 0;        // the stream slot it runs on; when it was last rung (the slots are handed out LRU)
     uint32_t misses = 0;                              // calls in a row that wanted this unit while every slot was taken (resident_admit)
   } res[kResUnits];
-  eppk::ResidentArgs* d_res_args = nullptr;
-  uint32_t* d_res_wl = nullptr; uint32_t res_wl_cap = 0;     // the resident workgroup's work list (its pick_quad_kernel form): total[32] | cnt[16] | list[16][cap]
+  DBuf<eppk::ResidentArgs> d_res_args;
+  DBuf<uint32_t> d_res_wl; uint32_t res_wl_cap = 0;     // the resident workgroup's work list (its pick_quad_kernel form): total[32] | cnt[16] | list[16][cap]
   uint64_t res_batches = 0, res_starts = 0;
-  uint32_t* d_learn = nullptr; size_t learn_cap = 0;          // learn words of the pick in front of a LEARN update (pick_quad_kernel<..., LEARN>)
+  DBuf<uint32_t> d_learn;                                     // learn words of the pick in front of a LEARN update (pick_quad_kernel<..., LEARN>)
   bool quiet_rows = false;        // a host-buffer launch is being enqueued: its kernels raise "row out of range" on a word of their own
                                   // (the call reports the row itself), not on the sticky flag of the *_device entry points
   uint32_t host_flags = 0;        // sticky launch-status flags raised by the host side (EPPK_LAUNCH_LEARN_FAILED)
-  void* d_tk_reqs = nullptr; uint64_t* d_tk_mask = nullptr; int32_t* d_tk_pick = nullptr; double* d_tk_score = nullptr;  // eppk_pick_topk
-  eppk_pod_row* h_rows = nullptr; eppk_pod_row* d_rows = nullptr;  // raw pod rows of a publish (pinned staging + device copy)
+  DBuf<void> d_tk_reqs; DBuf<uint64_t> d_tk_mask; DBuf<int32_t> d_tk_pick; DBuf<double> d_tk_score;  // eppk_pick_topk
+  HBuf<eppk_pod_row> h_rows; DBuf<eppk_pod_row> d_rows;  // raw pod rows of a publish (pinned staging + device copy)
 
   // metric predicates of the Filter phase (SEMANTICS.md §2c; eppk_filter.hip.h).  The planes are rebuilt in front of a filter launch
   // whenever the rows or the programs have changed since they were built (filt_gen: advanced by a publish, by eppk_set_filters and by
   // every assumed-load bump, which edits d_rows in place) or the launch goes to another stream than the build did.
   eppk::KFilter filt{};
-  uint64_t* d_fplanes = nullptr;
+  DBuf<uint64_t> d_fplanes;
   uint64_t filt_gen = 1, filt_built = 0; hipStream_t filt_stream = nullptr;
-  uint64_t* d_fmask = nullptr; size_t fmask_rows = 0;       // mask rows of eppk_pick_filtered_device (they never leave the device)
-  uint8_t* d_fcls = nullptr; uint8_t* d_fverdict = nullptr; // host-buffer forms: max_batch bytes each
+  DBuf<uint64_t> d_fmask;                                   // mask rows of eppk_pick_filtered_device (they never leave the device)
+  DBuf<uint8_t> d_fcls; DBuf<uint8_t> d_fverdict;           // host-buffer forms: max_batch bytes each
 
   // picker "best-score under per-pod caps" (SEMANTICS.md §3d; eppk_bounded.hip.h).  Scratch of the resolve, grown on demand:
   uint32_t bound_chunk = eppk::kBoundDefaultChunk;          // rows per chunk (EPPK_BOUND_CHUNK: a power of two >= 64)
-  uint32_t* d_bd_hist = nullptr; size_t bd_hist_words = 0;  // [chunks][n_pods] bids of a round per chunk, then their exclusive prefix
-  uint8_t* d_bd_state = nullptr; size_t bd_state_rows = 0;  // a byte per request when the caller takes no ranks
-  uint32_t* d_bd_pods = nullptr;                            // [4][EPPK_MAX_PODS]: room, load (no d_load), and the host forms' cap and load
-  int32_t* d_bd_list = nullptr; double* d_bd_lscore = nullptr; size_t bd_list_rows = 0;   // lists of eppk_pick_bounded_device (x EPPK_MAX_TOPK)
-  int32_t* d_bd_opick = nullptr; double* d_bd_oscore = nullptr; uint8_t* d_bd_orank = nullptr; size_t bd_out_rows = 0;   // results of the host forms
+  DBuf<uint32_t> d_bd_hist;                                 // [chunks][n_pods] bids of a round per chunk, then their exclusive prefix
+  DBuf<uint8_t> d_bd_state;                                 // a byte per request when the caller takes no ranks
+  DBuf<uint32_t> d_bd_pods;                                 // [4][EPPK_MAX_PODS]: room, load (no d_load), and the host forms' cap and load
+  DBuf<int32_t> d_bd_list; DBuf<double> d_bd_lscore;        // lists of eppk_pick_bounded_device (x EPPK_MAX_TOPK)
+  DBuf<int32_t> d_bd_opick; DBuf<double> d_bd_oscore; DBuf<uint8_t> d_bd_orank;   // results of the host forms
   // ... with priority bands (SEMANTICS.md §3e; eppk_banded.hip.h): the band order of a batch of more than one chunk
-  uint32_t* d_bn_perm = nullptr; size_t bn_perm_rows = 0;   // place in the band order -> request
-  uint32_t* d_bn_bh = nullptr; size_t bn_bh_words = 0;      // seg[0 .. 8] (kBandSegWords words), then [chunks][8] rows per band / their offsets
-  uint8_t* d_bn_band = nullptr; size_t bn_band_rows = 0;    // band bytes of the host forms
+  DBuf<uint32_t> d_bn_perm;                                 // place in the band order -> request
+  DBuf<uint32_t> d_bn_bh;                                   // seg[0 .. 8] (kBandSegWords words), then [chunks][8] rows per band / their offsets
+  DBuf<uint8_t> d_bn_band;                                  // band bytes of the host forms
   // ... in cost units (SEMANTICS.md §3f; eppk_costed.hip.h)
-  uint32_t* d_cs_acc = nullptr; size_t cs_acc_words = 0;    // [EPPK_MAX_PODS] takers' totals of a round, until the next scan pass folds them into the load
-  uint32_t* d_cs_cost = nullptr; size_t cs_cost_rows = 0;   // costs of the host forms (per request)
+  DBuf<uint32_t> d_cs_acc;                                  // [EPPK_MAX_PODS] takers' totals of a round, until the next scan pass folds them into the load
+  DBuf<uint32_t> d_cs_cost;                                 // costs of the host forms (per request)
 
   // measurement
   bool prof = false;
@@ -221,7 +235,7 @@ struct eppk_ctx {
   uint32_t launches = 0;
 
   uint64_t h_holes[64] = {0};         // holes of the last published snapshot, lane-transposed (bit j of word l = pod j*64+l)
-  void* d_rm = nullptr;               // [64] LW device copy of a scrub mask
+  DBuf<void> d_rm;                    // [64] LW device copy of a scrub mask
 
   hipEvent_t last_done = nullptr;     // completion event riding on the most recent pick launch (profiling), else null
   hipStream_t last_stream = nullptr;  // the stream of that launch
@@ -254,18 +268,18 @@ struct eppk_ctx {
   // still fails with EPPK_ERR_ARG naming the row (from _end), and delivers nothing.  Batches of at most host_check_max rows keep the
   // host loop (cheaper than a second launch and its event: 2048 requests 33 us with the loop, 41-45 with the kernel;
   // 64k staged: 478 vs 402 us, profiles/r03_z_small_batch_latency.txt).  EPPK_HOST_CHECK_MAX overrides.
-  struct RowCheck { uint32_t* h_bad = nullptr; uint32_t* h_bad_dev = nullptr; hipStream_t st = nullptr; hipEvent_t done = nullptr;
+  struct RowCheck { HBuf<uint32_t> h_bad; hipStream_t st = nullptr; hipEvent_t done = nullptr;
                     bool pending = false, side = false; const char* who = nullptr; };
   RowCheck check;
   uint32_t host_check_max = 2048;
   // One work-list buffer per STREAM that has launched picks (launches of one stream are ordered, so a buffer is never written
   // while an earlier launch still reads it; launches of different streams never share one).  More than kDeferSets distinct streams:
   // the later ones stay on pick_fast_kernel.
-  struct DeferSet { hipStream_t st = nullptr; bool used = false; uint32_t* d = nullptr; size_t words = 0; uint32_t uses = 0; };   // d: total[2] | cnt[segs] | list[segs][cap]
+  struct DeferSet { hipStream_t st = nullptr; bool used = false; DBuf<uint32_t> d; uint32_t uses = 0; };   // d (capacity: words): total[2] | cnt[segs] | list[segs][cap]
   DeferSet dsets[8];
   // Reports: every quad launch owns the next slot of a ring of pinned host words; the work-list kernel stores the launch's deferred
   // count there (kReportPending until then); the host consumes the slots in order, whenever it passes by.
-  volatile uint32_t* h_reports = nullptr;      // pinned [kReportRing]
+  HBuf<volatile uint32_t> h_reports;           // pinned [kReportRing]
   uint32_t rep_n[4096] = {0};                  // requests of the launch that owns the slot (kReportRing entries)
   uint8_t rep_masked[4096] = {0};              // ... and whether it was a masked batch
   uint64_t rep_unread = 0;                     // first launch whose report has not been consumed
@@ -332,6 +346,16 @@ int fail(eppk_ctx* c, int code, const std::string& msg) {
     if (e_ != hipSuccess)                                                                        \
       return fail((c), EPPK_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));      \
   } while (0)
+
+// eppk::grow for the buffers of a context.  A call that REPLACES memory parks this context's resident units and drains the device
+// first (device_sync: what is queued on any stream may still read the old buffers, and hipFree would sit out a polling unit's idle
+// time-out); a first allocation waits for nothing.  A failed allocation leaves the group empty: EPPK_ERR_NOMEM, and a retry starts clean.
+int device_sync(eppk_ctx* c);
+int ctx_grow(eppk_ctx* c, size_t need, std::initializer_list<eppk::Member> bufs, bool* fresh = nullptr) {
+  std::string what;
+  const int rc = eppk::grow([c] { return device_sync(c); }, need, bufs, fresh, &what);
+  return rc == EPPK_ERR_NOMEM ? fail(c, rc, what) : rc;
+}
 
 inline double h_clamp01(double s) {
   if (!(s >= 0.0)) return 0.0;
@@ -524,16 +548,13 @@ int launch_pick(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t
     // header: total[2] | done counters[17] (TAIL) | cnt | list | masked batches: the rows a wavefront scores itself when its loop is over
     // (pick_quad_body: my_xr / my_xs -- an index and 16 lanes x 8 bytes of state per request)
     const size_t words = 32u + (size_t)quad_segs + (size_t)quad_segs * defer_cap * (masked ? 34u : 1u);
-    if (words > dset->words) {             // grow this stream's buffer (rare: its first launch, or a larger batch than ever before)
-      { const int rcp = resident_park(c); if (rcp) return rcp; }      // (hipFree waits for the device)
-      HIPCHK(c, hipStreamSynchronize(st));
-      if (dset->d) HIPCHK(c, hipFree(dset->d));
-      dset->d = nullptr; dset->words = 0;
-      HIPCHK(c, hipMalloc((void**)&dset->d, words * 4u));
+    bool fresh = false;                    // this stream's buffer (new memory is rare: the stream's first launch, or a larger batch than ever before)
+    { const int rcg = ctx_grow(c, words, {{dset->d, 4u, "work list of a pick stream"}}, &fresh); if (rcg) return rcg; }
+    if (fresh) {
       HIPCHK(c, hipMemsetAsync(dset->d, 0, 128, st)); // the two total counters and the done counters -- on the LAUNCH stream: a null-stream memset is not ordered
                                                        // ahead of kernels on a non-blocking stream (the first launch of a stream could read a
                                                        // garbage total: found when the work-list pass got faster, tests/test_gpu_quad.py)
-      dset->words = words; dset->uses = 0;
+      dset->uses = 0;
     }
     rep_slot = (uint32_t)(c->quad_launches % kReportRing);
     c->h_reports[rep_slot] = kReportPending;
@@ -773,19 +794,13 @@ int resident_ensure(eppk_ctx* c) {            // control blocks, argument block,
     const uint32_t nblk = (c->resident_max + 3u) / 4u, per_wave = (nblk + 15u) / 16u;
     c->res_wl_cap = 4u * (per_wave ? per_wave : 1u);
     const size_t words = 32u + 16u + 16u * (size_t)c->res_wl_cap * 34u;       // (... | masked single picks: the rows a wavefront parks, pick_quad_body my_xr / my_xs)
-    uint32_t* wl = nullptr;
-    HIPCHK(c, hipMalloc((void**)&wl, words * 4u * eppk_ctx::kResUnits));      // (one work list per unit: two units may be scoring at once)
-    if (hipMemset(wl, 0, words * 4u * eppk_ctx::kResUnits) != hipSuccess) { (void)hipFree(wl); return fail(c, EPPK_ERR_DEVICE, "resident path: hipMemset of the work lists failed"); }
-    c->d_res_wl = wl;
+    { const int rcg = ctx_grow(c, words * eppk_ctx::kResUnits, {{c->d_res_wl, 4u, "resident work lists"}}); if (rcg) return rcg; }      // (one work list per unit: two units may be scoring at once)
+    if (hipMemset(c->d_res_wl, 0, words * 4u * eppk_ctx::kResUnits) != hipSuccess) { c->d_res_wl.reset(); return fail(c, EPPK_ERR_DEVICE, "resident path: hipMemset of the work lists failed"); }
   }
   for (eppk_ctx::ResidentUnit& u : c->res) {
-    if (!u.h_ctl) {
-      eppk::ResidentCtl* h = nullptr;
-      HIPCHK(c, hipHostMalloc((void**)&h, sizeof(eppk::ResidentCtl), hipHostMallocDefault));
-      std::memset(h, 0, sizeof(eppk::ResidentCtl));
-      u.h_ctl = h;
-    }
-    if (!u.h_ctl_dev) HIPCHK(c, hipHostGetDevicePointer((void**)&u.h_ctl_dev, u.h_ctl, 0));
+    bool fresh = false;
+    { const int rcg = ctx_grow(c, 1u, {{u.h_ctl, sizeof(eppk::ResidentCtl), "resident control block"}}, &fresh); if (rcg) return rcg; }
+    if (fresh) std::memset(u.h_ctl, 0, sizeof(eppk::ResidentCtl));
   }
   // The streams the resident kernels are launched on: kResSlots of them, at the HIGHEST stream priority.  The runtime multiplexes the
   // streams of one priority class over a few hardware queues (four by default), and a kernel that never ends blocks its queue: a second
@@ -804,16 +819,15 @@ int resident_ensure(eppk_ctx* c) {            // control blocks, argument block,
   }
   if (c->slots && !c->d_res_sortwl) {       // LEARN units (two at most): a device copy of a batch's rows, its learn words, a sort work list each
     const size_t rm = c->resident_max ? c->resident_max : 1u;
-    HIPCHK(c, hipMalloc((void**)&c->d_res_rows, 2u * rm * c->stride));
-    HIPCHK(c, hipMalloc((void**)&c->d_res_learn, 2u * rm * 4u));
     const size_t wl_words = 4u + rm * (c->cfg.max_blocks ? c->cfg.max_blocks : 1u);
-    uint32_t* wl = nullptr;
-    HIPCHK(c, hipMalloc((void**)&wl, 2u * wl_words * 4u));
-    if (hipMemset(wl, 0, 2u * wl_words * 4u) != hipSuccess) { (void)hipFree(wl); return fail(c, EPPK_ERR_DEVICE, "resident path: hipMemset of the sort work lists failed"); }
-    c->d_res_sortwl = wl;
+    { const int rcg = ctx_grow(c, 2u, {{c->d_res_rows, rm * c->stride, "resident row copies"}, {c->d_res_learn, rm * 4u, "resident learn words"},
+                                       {c->d_res_sortwl, wl_words * 4u, "resident sort work lists"}}); if (rcg) return rcg; }
+    if (hipMemset(c->d_res_sortwl, 0, 2u * wl_words * 4u) != hipSuccess) {
+      c->d_res_rows.reset(); c->d_res_learn.reset(); c->d_res_sortwl.reset();
+      return fail(c, EPPK_ERR_DEVICE, "resident path: hipMemset of the sort work lists failed");
+    }
   }
-  HIPCHK(c, hipMalloc((void**)&c->d_res_args, sizeof(eppk::ResidentArgs) * eppk_ctx::kResUnits));
-  return EPPK_OK;
+  return ctx_grow(c, eppk_ctx::kResUnits, {{c->d_res_args, sizeof(eppk::ResidentArgs), "resident argument blocks"}});
 }
 // `outstanding`: a doorbell has been rung that the workgroup which just left did not answer (the in-call restart of resident_wait): the
 // new workgroup must take it at once (seen = seq - 1).  Otherwise the last doorbell HAS been answered: seen = seq, or the fresh
@@ -855,7 +869,7 @@ int resident_start(eppk_ctx* c, uint32_t unit, bool outstanding = false) {
   uint32_t bell_now = __atomic_load_n(&u.h_ctl->bell, __ATOMIC_ACQUIRE);
   if (bell_now == eppk::kResQuit) __atomic_store_n(&u.h_ctl->bell, seen, __ATOMIC_RELEASE);
   __atomic_store_n(&u.h_ctl->state, eppk::kResRunning, __ATOMIC_RELEASE);
-  eppk::ResidentCtl* ctl = u.h_ctl_dev;
+  eppk::ResidentCtl* ctl = u.h_ctl.dev();
   const eppk::ResidentArgs* args = c->d_res_args + unit;
   uint32_t seen_arg = seen;
   unsigned long long max_idle = 30000ull;                 // ~20-50 ms of polls over PCIe, then the workgroup leaves by itself
@@ -957,10 +971,10 @@ int resident_ring(eppk_ctx* c, uint32_t n_reqs, bool masked, uint32_t k, uint32_
     if (rc) return rc;
     eppk::ResidentArgs a{};
     a.sn = make_ksnap(c); a.ix = make_kindex(c); a.tl = c->tail; a.chain = c->kchain;
-    a.buf[0] = {(const uint8_t*)c->h_reqs_dev, c->h_mask_dev, c->h_pick_dev, c->h_score_dev};
+    a.buf[0] = {(const uint8_t*)c->h_reqs.dev(), c->h_mask.dev(), c->h_pick.dev(), c->h_score.dev()};
     for (uint32_t sset = 0; sset < EPPK_STAGE_SETS; ++sset) {
       const eppk_ctx::StageSet& ss = c->stage[sset];
-      a.buf[1u + sset] = {(const uint8_t*)ss.h_reqs_dev, ss.h_mask_dev, ss.h_pick_dev, ss.h_score_dev};
+      a.buf[1u + sset] = {(const uint8_t*)ss.h_reqs.dev(), ss.h_mask.dev(), ss.h_pick.dev(), ss.h_score.dev()};
     }
     a.stride = c->stride; a.pwn = (c->cfg.max_blocks + 1u) * c->pterm_ld;
     if (++c->res_gen == 0u) c->res_gen = 1u;
@@ -973,7 +987,7 @@ int resident_ring(eppk_ctx* c, uint32_t n_reqs, bool masked, uint32_t k, uint32_
       a.act = c->have_snapshot ? c->snap[c->cur].act_t : nullptr;
       a.limit = c->limit; a.epoch = c->index_epoch; a.max_blocks = c->cfg.max_blocks; a.max_pods = c->cfg.max_pods;
       a.set_ctl = c->set_ctl;
-      a.ix_report = c->h_set_report_dev + 2;
+      a.ix_report = c->h_set_report.dev() + 2;
     }
     eppk::ResidentArgs all[eppk_ctx::kResUnits];
     const size_t wl_words = 32u + 16u + 16u * (size_t)c->res_wl_cap * 34u;
@@ -1037,14 +1051,9 @@ int run_pick(eppk_ctx* c, const uint8_t* d_reqs, uint32_t n_reqs, const uint64_t
   const uint32_t per = E ? (n_reqs + E - 1u) / E : n_reqs;
   const size_t J = (c->n_pods + 63u) / 64u;
   const uint32_t ok = random ? 1u : k;                        // entries per request in the caller's arrays
-  if (random && (size_t)per * k > c->rs_cap) {                // fallback lists of one epoch
-    { const int rcp = resident_park(c); if (rcp) return rcp; }
-    HIPCHK(c, hipStreamSynchronize(st));
-    (void)hipFree(c->d_rs_pick); (void)hipFree(c->d_rs_score);
-    c->d_rs_pick = nullptr; c->d_rs_score = nullptr; c->rs_cap = 0;
-    HIPCHK(c, hipMalloc((void**)&c->d_rs_pick, (size_t)per * k * 4u));
-    HIPCHK(c, hipMalloc((void**)&c->d_rs_score, (size_t)per * k * 8u));
-    c->rs_cap = (size_t)per * k;
+  if (random && n_reqs) {                                     // fallback lists of one epoch
+    const int rcg = ctx_grow(c, (size_t)per * k, {{c->d_rs_pick, 4u, "random-top-k fallback picks"}, {c->d_rs_score, 8u, "random-top-k fallback scores"}});
+    if (rcg) return rcg;
   }
   for (uint32_t lo = 0; lo < n_reqs; lo += per) {
     const uint32_t cnt = n_reqs - lo < per ? n_reqs - lo : per;
@@ -1096,17 +1105,14 @@ int by_lane_word(const eppk_ctx* c, F&& f) {
 // events: include/eppk.h), so one work list serves them all.
 int sortwl_begin(eppk_ctx* c, uint64_t n_pairs, eppk::SortWl* sw) {
   const uint32_t want = (uint32_t)(n_pairs < (1ull << 24) ? n_pairs : (1ull << 24));
-  if (!c->sortwl || want > c->sortwl_cap) {
-    { const int rcs_ = device_sync(c); if (rcs_) return rcs_; }                 // (rare: the first insert, or a larger launch than ever before)
-    if (c->sortwl) HIPCHK(c, hipFree(c->sortwl));
-    c->sortwl = nullptr; c->sortwl_cap = 0;
-    const uint32_t cap = want < 4096u ? 4096u : want;
-    HIPCHK(c, hipMalloc((void**)&c->sortwl, (4u + (size_t)cap) * 4u));
+  bool fresh = false;                     // (new memory is rare: the first insert, or a larger launch than ever before)
+  { const int rcg = ctx_grow(c, 4u + (size_t)(want < 4096u ? 4096u : want), {{c->sortwl, 4u, "sort work list"}}, &fresh); if (rcg) return rcg; }
+  if (fresh) {
     HIPCHK(c, hipMemset(c->sortwl, 0, 16));
     { const int rcs_ = device_sync(c); if (rcs_) return rcs_; }
-    c->sortwl_cap = cap; c->sort_uses = 0;
+    c->sort_uses = 0;
   }
-  sw->wl = c->sortwl; sw->cap = c->sortwl_cap; sw->which = c->sort_uses & 1u;
+  sw->wl = c->sortwl; sw->cap = (uint32_t)(c->sortwl.cap() - 4u); sw->which = c->sort_uses & 1u;
   ++c->sort_uses;
   return EPPK_OK;
 }
@@ -1134,7 +1140,7 @@ int sortwl_finish(eppk_ctx* c, const eppk::SortWl& sw, hipStream_t st) {
   }
   const uint32_t grid = rebuild ? (uint32_t)std::min<size_t>(((size_t)c->slots + 2u + 255u) / 256u, 4096u) : 64u;
   hipLaunchKernelGGL(eppk::index_canon_kernel, dim3(grid), dim3(256), 0, st, c->keys, c->lists, c->slots, make_settab(c), sw.wl, sw.cap, sw.which, rebuild ? 1u : 0u,
-                     c->h_set_report_dev);
+                     c->h_set_report.dev());
   HIPCHK(c, hipGetLastError());
   return EPPK_OK;
 }
@@ -1160,7 +1166,7 @@ int index_reclaim(eppk_ctx* c, hipStream_t st) {
 
 // Remove every pod of the lane-transposed set `holes` from every index row (one pass; rows that become empty are tombstoned).
 int index_scrub(eppk_ctx* c, const uint64_t* holes) {
-  if (!c->d_rm) HIPCHK(c, hipMalloc(&c->d_rm, 64u * 8u));
+  { const int rcg = ctx_grow(c, 64u, {{c->d_rm, 8u, "scrub mask"}}); if (rcg) return rcg; }
   uint8_t packed[64 * 8];
   for (uint32_t l = 0; l < 64u; ++l) {           // narrow the u64 lane words to the context's lane-word type
     if (c->lw_bytes == 8) std::memcpy(packed + l * 8u, &holes[l], 8u);
@@ -1231,16 +1237,6 @@ int ixc_sum(eppk_ctx* c, uint32_t field, unsigned long long* out) {
   return EPPK_OK;
 }
 
-int ensure_tmp(eppk_ctx* c, size_t bytes) {
-  if (bytes <= c->d_tmp_bytes) return EPPK_OK;
-  { const int rcp = resident_park(c); if (rcp) return rcp; }
-  if (c->d_tmp) HIPCHK(c, hipFree(c->d_tmp));
-  c->d_tmp = nullptr; c->d_tmp_bytes = 0;
-  HIPCHK(c, hipMalloc(&c->d_tmp, bytes));
-  c->d_tmp_bytes = bytes;
-  return EPPK_OK;
-}
-
 }  // namespace
 
 // ================================================================================================
@@ -1280,6 +1276,7 @@ int eppk_create(const eppk_cfg* cfg, eppk_ctx** out) {
   c->cfg = *cfg;
   auto bail = [&](int code) { std::string m = c->err; eppk_destroy(c); fail(nullptr, code, m); return code; };
 #define CHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { c->err = std::string(#expr) + ": " + hipGetErrorString(e_); return bail(EPPK_ERR_DEVICE); } } while (0)
+#define MK(need, ...) do { const int rc_ = ctx_grow(c, (need), __VA_ARGS__); if (rc_) return bail(rc_); } while (0)
   CHK(hipSetDevice(cfg->device));
   hipDeviceProp_t prop;
   CHK(hipGetDeviceProperties(&prop, cfg->device));
@@ -1316,7 +1313,7 @@ int eppk_create(const eppk_cfg* cfg, eppk_ctx** out) {
     const int v = atoi(qt);
     if (v >= 64 && v <= EPPK_QUAD_MAX_THREADS && v % 64 == 0) c->quad_threads = (uint32_t)v;
   }
-  CHK(hipHostMalloc((void**)&c->h_reports, (kReportRing + 1u) * sizeof(uint32_t), hipHostMallocDefault));   // (+ 1: the word the warm-up launch reports to)
+  MK(kReportRing + 1u, {{c->h_reports, sizeof(uint32_t), "report ring"}});   // (+ 1: the word the warm-up launch reports to)
   for (uint32_t i = 0; i <= kReportRing; ++i) c->h_reports[i] = 0u;
   c->lw_bytes = cfg->max_pods <= 1024 ? 2 : cfg->max_pods <= 2048 ? 4 : 8;
   c->npl = cfg->max_blocks <= 63 ? 6 : 9;
@@ -1386,7 +1383,7 @@ int eppk_create(const eppk_cfg* cfg, eppk_ctx** out) {
     L.bytes = off + 256u;                      // the LAST dword is the fast kernel's launch-status word (kBlobStatusTail)
     for (int b = 0; b < 2; ++b) {
       SnapBuf& s = c->snap[b];
-      CHK(hipMalloc((void**)&s.blob, L.bytes));
+      MK(L.bytes, {{s.blob, 1u, "snapshot blob"}});
       CHK(hipMemset(s.blob + L.bytes - 256u, 0, 256u));
       s.base = (double*)(s.blob + L.base); s.post[0] = (double*)(s.blob + L.post0); s.post[1] = (double*)(s.blob + L.post1);
       s.queue = (uint32_t*)(s.blob + L.queue); s.kv = (double*)(s.blob + L.kv);
@@ -1401,18 +1398,17 @@ int eppk_create(const eppk_cfg* cfg, eppk_ctx** out) {
     std::vector<double> tab((size_t)ld * ld, 0.0);
     for (uint32_t n = 1; n <= cfg->max_blocks; ++n)
       for (uint32_t cnt = 0; cnt <= n; ++cnt) tab[(size_t)n * ld + cnt] = h_clamp01((double)cnt / (double)n) * c->tail.wp;
-    CHK(hipMalloc((void**)&c->pterm, tab.size() * 8u));
+    MK(tab.size(), {{c->pterm, 8u, "prefix terms"}});
     CHK(hipMemcpy(c->pterm, tab.data(), tab.size() * 8u, hipMemcpyHostToDevice));
     c->pterm_ld = ld;
   }
-  CHK(hipHostMalloc((void**)&c->h_rows, (size_t)cfg->max_pods * sizeof(eppk_pod_row), hipHostMallocDefault));
-  CHK(hipMalloc((void**)&c->d_rows, (size_t)cfg->max_pods * sizeof(eppk_pod_row)));
-  CHK(hipMalloc((void**)&c->stats, (4 + 2 * (size_t)kStatSlots * kStatBanks) * sizeof(unsigned long long)));
+  MK(cfg->max_pods, {{c->h_rows, sizeof(eppk_pod_row), "pod rows (pinned)"}, {c->d_rows, sizeof(eppk_pod_row), "pod rows"}});
+  MK(4 + 2 * (size_t)kStatSlots * kStatBanks, {{c->stats, sizeof(unsigned long long), "statistics"}});
   CHK(hipMemset(c->stats, 0, (4 + 2 * (size_t)kStatSlots * kStatBanks) * sizeof(unsigned long long)));
-  CHK(hipMalloc((void**)&c->ixc, eppk::kIxShards * 8u * sizeof(unsigned long long)));
+  MK(eppk::kIxShards * 8u, {{c->ixc, sizeof(unsigned long long), "index counters"}});
   CHK(hipMemset(c->ixc, 0, eppk::kIxShards * 8u * sizeof(unsigned long long)));
-  CHK(hipMalloc((void**)&c->d_ixl, sizeof(eppk::IxLaunch)));
-  CHK(hipMalloc((void**)&c->d_status, 2 * sizeof(uint32_t)));
+  MK(1u, {{c->d_ixl, sizeof(eppk::IxLaunch), "insert verdict"}});
+  MK(2u, {{c->d_status, sizeof(uint32_t), "launch status"}});
   CHK(hipMemset(c->d_status, 0, 2 * sizeof(uint32_t)));
   if (cfg->index_slots) {
     // PHYSICAL slots = words of the key table: twice the API's index_slots, because five of a bucket's eight words hold keys (the other
@@ -1426,10 +1422,10 @@ int eppk_create(const eppk_cfg* cfg, eppk_ctx** out) {
     // ONE allocation: pod-set rows first, the key table behind them (the fast kernel reads both through one descriptor)
     c->rows_bytes = (((size_t)c->slots + 3u) * 64u * (size_t)c->lw_bytes + 255u) & ~(size_t)255u;
     c->index_bytes = c->rows_bytes + ((size_t)c->slots + 2u) * 8u;
-    CHK(hipMalloc(&c->bitmaps, c->index_bytes));
+    MK(c->index_bytes, {{c->bitmaps, 1u, "prefix index"}});
     c->keys = (uint64_t*)((uint8_t*)c->bitmaps + c->rows_bytes);
     CHK(hipMemset(c->bitmaps, 0, c->index_bytes));
-    CHK(hipMalloc((void**)&c->rstamps, 2u * 4u));
+    MK(2u, {{c->rstamps, 4u, "reserved-row stamps"}});
     CHK(hipMemset(c->rstamps, 0, 2u * 4u));
     const char* le = getenv("EPPK_LISTS");
     c->list_routes = !(le && atoi(le) == 0);
@@ -1438,16 +1434,15 @@ int eppk_create(const eppk_cfg* cfg, eppk_ctx** out) {
       // prefix share one); all-zero = every line free
       c->sets_cap = c->slots / 16u < 1024u ? 1024u : c->slots / 16u;
       const size_t nd = ((size_t)c->slots + 4u) * eppk::kListDwords, ns = (size_t)c->sets_cap * eppk::kListDwords;
-      CHK(hipMalloc((void**)&c->lists, (nd + ns) * 4u));
+      MK(nd + ns, {{c->lists, 4u, "pod lists and set table"}});
       hipLaunchKernelGGL(eppk::lists_fill_kernel, dim3(1024), dim3(256), 0, c->stream, c->lists, nd);
       CHK(hipGetLastError());
       CHK(hipMemsetAsync(c->lists + nd, 0, ns * 4u, c->stream));
-      CHK(hipMalloc((void**)&c->set_ctl, 2u * 4u));
+      MK(2u, {{c->set_ctl, 4u, "set-table counters"}});
       CHK(hipMemsetAsync(c->set_ctl, 0, 2u * 4u, c->stream));
-      CHK(hipHostMalloc((void**)&c->h_set_report, 3u * 4u, hipHostMallocDefault));
+      MK(3u, {{c->h_set_report, 4u, "set-table report"}});
       c->h_set_report[0] = c->h_set_report[1] = c->h_set_report[2] = 0u;
-      CHK(hipMalloc((void**)&c->d_crossed, ((size_t)c->slots / kBucket + 31u) / 32u * 4u));
-      CHK(hipHostGetDevicePointer((void**)&c->h_set_report_dev, c->h_set_report, 0));
+      MK(((size_t)c->slots / kBucket + 31u) / 32u, {{c->d_crossed, 4u, "reclaim bitmap"}});
       CHK(hipStreamSynchronize(c->stream));
     }
   }
@@ -1455,6 +1450,7 @@ int eppk_create(const eppk_cfg* cfg, eppk_ctx** out) {
   // the resident path's default limit: with pick_quad_kernel's body behind the doorbell 64 requests take 16.6 us (21.1 launched), with
   // pick_fast_kernel's body alone 24.5 -- 32 stays the limit there
   if (c->resident_on && !resident_max_set && resident_quad(c)) c->resident_max = 64;
+#undef MK
 #undef CHK
   *out = c;
   return EPPK_OK;
@@ -1473,53 +1469,18 @@ void eppk_destroy(eppk_ctx* c) {
   }
   (void)hipSetDevice(c->cfg.device);
   (void)resident_park(c);
-  for (eppk_ctx::ResidentUnit& u : c->res) if (u.h_ctl) (void)hipHostFree(u.h_ctl);
-  for (hipStream_t st : c->res_slot_stream) if (st) (void)hipStreamDestroy(st);
-  (void)hipFree(c->d_res_args);
-  (void)hipFree(c->d_res_wl);
-  (void)hipFree(c->d_res_rows); (void)hipFree(c->d_res_learn); (void)hipFree(c->d_res_sortwl);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (int b = 0; b < 2; ++b) (void)hipFree(c->snap[b].blob);
-  (void)hipFree(c->bitmaps); (void)hipFree(c->rstamps); (void)hipFree(c->lists); (void)hipFree(c->set_ctl); (void)hipHostFree(c->h_set_report); (void)hipFree(c->d_crossed); (void)hipFree(c->sortwl); (void)hipFree(c->d_ixl);
-  (void)hipFree(c->d_at); (void)hipFree(c->d_av); (void)hipFree(c->d_sk); (void)hipFree(c->d_so);
-  if (c->wait_ev) (void)hipEventDestroy(c->wait_ev);
-  (void)hipFree(c->stats); (void)hipFree(c->pterm); (void)hipFree(c->d_status); (void)hipFree(c->ixc);
-  (void)hipFree(c->d_tk_reqs); (void)hipFree(c->d_tk_mask); (void)hipFree(c->d_tk_pick); (void)hipFree(c->d_tk_score);
-  (void)hipFree(c->d_reqs); (void)hipFree(c->d_mask); (void)hipFree(c->d_pick); (void)hipFree(c->d_score); (void)hipFree(c->d_tmp);
-  for (uint32_t b = 0; b < 8; ++b) (void)hipFree(c->dsets[b].d);
-  for (auto& s : c->stage) {
-    if (s.st) { (void)hipStreamSynchronize(s.st); (void)hipStreamDestroy(s.st); }
-    if (s.picked) (void)hipEventDestroy(s.picked);
-    if (s.st_copy) { (void)hipStreamSynchronize(s.st_copy); (void)hipStreamDestroy(s.st_copy); }
-    if (s.copied) (void)hipEventDestroy(s.copied);
-    if (s.st_check) { (void)hipStreamSynchronize(s.st_check); (void)hipStreamDestroy(s.st_check); }
-    if (s.checked) (void)hipEventDestroy(s.checked);
-    if (s.h_bad) (void)hipHostFree(s.h_bad);
-    (void)hipFree(s.d_reqs); (void)hipFree(s.d_mask); (void)hipFree(s.d_pick); (void)hipFree(s.d_score);
-    if (s.h_reqs) (void)hipHostFree(s.h_reqs);
-    if (s.h_mask) (void)hipHostFree(s.h_mask);
-    if (s.h_pick) (void)hipHostFree(s.h_pick);
-    if (s.h_score) (void)hipHostFree(s.h_score);
-  }
-  if (c->learned) (void)hipEventDestroy(c->learned);
-  if (c->learn_words_free) (void)hipEventDestroy(c->learn_words_free);
-  if (c->check.st) { (void)hipStreamSynchronize(c->check.st); (void)hipStreamDestroy(c->check.st); }
-  if (c->check.done) (void)hipEventDestroy(c->check.done);
-  if (c->check.h_bad) (void)hipHostFree(c->check.h_bad);
-  if (c->h_reports) (void)hipHostFree((void*)c->h_reports);
-  if (c->h_rows) (void)hipHostFree(c->h_rows);
-  (void)hipFree(c->d_fplanes); (void)hipFree(c->d_fmask); (void)hipFree(c->d_fcls); (void)hipFree(c->d_fverdict);
-  (void)hipFree(c->d_bd_hist); (void)hipFree(c->d_bd_state); (void)hipFree(c->d_bd_pods); (void)hipFree(c->d_bd_list); (void)hipFree(c->d_bd_lscore);
-  (void)hipFree(c->d_bd_opick); (void)hipFree(c->d_bd_oscore); (void)hipFree(c->d_bd_orank);
-  (void)hipFree(c->d_bn_perm); (void)hipFree(c->d_bn_bh); (void)hipFree(c->d_bn_band);
-  (void)hipFree(c->d_cs_acc); (void)hipFree(c->d_cs_cost);
-  (void)hipFree(c->d_rows); (void)hipFree(c->d_rm); (void)hipFree(c->d_rs_pick); (void)hipFree(c->d_rs_score); (void)hipFree(c->d_learn);
-  if (c->h_reqs) (void)hipHostFree(c->h_reqs);
-  if (c->h_mask) (void)hipHostFree(c->h_mask);
-  if (c->h_pick) (void)hipHostFree(c->h_pick);
-  if (c->h_score) (void)hipHostFree(c->h_score);
+  // every stream the context owns runs dry, then the events go, then the streams; the buffers free themselves with the context
+  // (destroyed in the order they always were: the resident slots first, the context's own stream last)
+  hipStream_t own[] = {c->res_slot_stream[0], c->res_slot_stream[1], c->res_slot_stream[2], c->res_slot_stream[3], c->stage[0].st, c->stage[0].st_copy,
+                       c->stage[0].st_check, c->stage[1].st, c->stage[1].st_copy, c->stage[1].st_check, c->check.st, c->stream};
+  static_assert(eppk_ctx::kResSlots == 4u && EPPK_STAGE_SETS == 2, "eppk_destroy names every stream the context owns");
+  for (hipStream_t st : own) if (st) (void)hipStreamSynchronize(st);
+  // (learn_words_stream is one of these or the CALLER's, which may be gone by now: not touched; the buffers' release waits for the device)
+  hipEvent_t evs[] = {c->wait_ev, c->stage[0].picked, c->stage[0].copied, c->stage[0].checked, c->stage[1].picked, c->stage[1].copied, c->stage[1].checked,
+                      c->learned, c->learn_words_free, c->check.done};
+  for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
+  for (hipStream_t st : own) if (st) (void)hipStreamDestroy(st);
   delete c;
 }
 
@@ -1603,7 +1564,7 @@ int eppk_index_insert(eppk_ctx* c, const uint64_t* hashes, const uint32_t* pods,
   if (n == 0) return EPPK_OK;
   HIPCHK(c, hipSetDevice(c->cfg.device));
   { const int rcf = learn_fence(c, c->stream); if (rcf) return rcf; }
-  int rc = ensure_tmp(c, (size_t)n * 12u);
+  int rc = ctx_grow(c, (size_t)n * 12u, {{c->d_tmp, 1u, "index staging"}});
   if (rc) return rc;
   uint64_t* d_h = (uint64_t*)c->d_tmp;
   uint32_t* d_p = (uint32_t*)((uint8_t*)c->d_tmp + (size_t)n * 8u);
@@ -1616,7 +1577,7 @@ int eppk_index_insert(eppk_ctx* c, const uint64_t* hashes, const uint32_t* pods,
   eppk::SortWl sw{};
   rc = sortwl_begin(c, n, &sw);
   if (rc) return rc;
-  hipLaunchKernelGGL(eppk::index_budget_kernel, dim3(1), dim3(64), 0, c->stream, c->ixc, c->limit, c->slots, (unsigned long long)n, c->d_ixl, c->h_set_report_dev + 2);
+  hipLaunchKernelGGL(eppk::index_budget_kernel, dim3(1), dim3(64), 0, c->stream, c->ixc, c->limit, c->slots, (unsigned long long)n, c->d_ixl, c->h_set_report.dev() + 2);
   rc = by_lane_word(c, [&](auto tag) {
     using LW = decltype(tag);
     hipLaunchKernelGGL((index_insert_kernel<LW>), dim3(grid), dim3(threads), 0, c->stream, c->keys, c->bitmaps, c->lists, c->rstamps, c->slots, c->shift,
@@ -1646,7 +1607,7 @@ int learn_picks(eppk_ctx* c, const void* d_reqs, const int32_t* d_picks, uint32_
   eppk::SortWl sw{};
   int rc = sortwl_begin(c, total, &sw);
   if (rc) return rc;
-  hipLaunchKernelGGL(eppk::index_budget_kernel, dim3(1), dim3(64), 0, st, c->ixc, c->limit, c->slots, (unsigned long long)total, c->d_ixl, c->h_set_report_dev + 2);
+  hipLaunchKernelGGL(eppk::index_budget_kernel, dim3(1), dim3(64), 0, st, c->ixc, c->limit, c->slots, (unsigned long long)total, c->d_ixl, c->h_set_report.dev() + 2);
   rc = by_lane_word(c, [&](auto tag) {
     using LW = decltype(tag);
     hipLaunchKernelGGL((index_insert_picks_kernel<LW>), dim3((uint32_t)grid64), dim3(threads), 0, st, c->keys, c->bitmaps, c->lists, c->rstamps, c->slots,
@@ -1721,7 +1682,7 @@ int eppk_index_selfcheck(eppk_ctx* c, uint64_t* n_bad) {
   if (!c->slots) return EPPK_OK;
   HIPCHK(c, hipSetDevice(c->cfg.device));
   { const int rcf = learn_fence(c, c->stream); if (rcf) return rcf; }
-  int rct = ensure_tmp(c, 256u * 8u);                                          // bad count | records | eight offenders in full (index_selfcheck_kernel)
+  int rct = ctx_grow(c, 256u * 8u, {{c->d_tmp, 1u, "index staging"}});                                          // bad count | records | eight offenders in full (index_selfcheck_kernel)
   if (rct) return rct;
   unsigned long long* d_bad = (unsigned long long*)c->d_tmp;
   HIPCHK(c, hipMemsetAsync(d_bad, 0, 256u * 8u, c->stream));
@@ -1817,7 +1778,7 @@ int eppk_index_trim_pods(eppk_ctx* c, uint32_t cap, uint64_t* n_removed) {
   { const int rcf = learn_fence(c, c->stream); if (rcf) return rcf; }
   // scratch: hist[4096][64] u32 | cutage[4096] u32 | over_t[64] u64 | removed u64
   const size_t hist_b = 4096u * (size_t)eppk::kTrimBins * 4u, cut_b = 4096u * 4u, over_b = 64u * 8u;
-  int rc = ensure_tmp(c, hist_b + cut_b + over_b + 8u);
+  int rc = ctx_grow(c, hist_b + cut_b + over_b + 8u, {{c->d_tmp, 1u, "index staging"}});
   if (rc) return rc;
   uint32_t* hist = (uint32_t*)c->d_tmp;
   uint32_t* cutage = (uint32_t*)((uint8_t*)c->d_tmp + hist_b);
@@ -1919,17 +1880,8 @@ int learn_words_fence(eppk_ctx* c, hipStream_t st) {
   c->learn_words_stream = st;
   return EPPK_OK;
 }
-// room for the learn words of n requests (grown behind a device synchronise: rare)
-int learn_ensure(eppk_ctx* c, size_t n) {
-  if (n <= c->learn_cap) return EPPK_OK;
-  { const int rcs_ = device_sync(c); if (rcs_) return rcs_; }
-  if (c->d_learn) HIPCHK(c, hipFree(c->d_learn));
-  c->d_learn = nullptr; c->learn_cap = 0;
-  const size_t cap = n < c->cfg.max_batch ? c->cfg.max_batch : n;
-  HIPCHK(c, hipMalloc((void**)&c->d_learn, cap * 4u));
-  c->learn_cap = cap;
-  return EPPK_OK;
-}
+// room for the learn words of n requests (max_batch at least)
+int learn_ensure(eppk_ctx* c, size_t n) { return ctx_grow(c, n < c->cfg.max_batch ? c->cfg.max_batch : n, {{c->d_learn, 4u, "learn words"}}); }
 }  // namespace
 
 int eppk_pick_learn_device(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, int32_t* d_out_pick,
@@ -1998,9 +1950,9 @@ __global__ void rows_check_kernel(const uint8_t* __restrict__ reqs, uint32_t str
     __hip_atomic_fetch_min(bad, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-int rows_check_launch(eppk_ctx* c, const void* rows_dev, uint32_t n, uint32_t* h_bad, uint32_t* h_bad_dev, hipStream_t st) {
+int rows_check_launch(eppk_ctx* c, const void* rows_dev, uint32_t n, const HBuf<uint32_t>& h_bad, hipStream_t st) {
   *h_bad = 0xFFFFFFFFu;
-  hipLaunchKernelGGL(rows_check_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, (const uint8_t*)rows_dev, c->stride, n, c->cfg.max_blocks, h_bad_dev);
+  hipLaunchKernelGGL(rows_check_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, (const uint8_t*)rows_dev, c->stride, n, c->cfg.max_blocks, h_bad.dev());
   HIPCHK(c, hipGetLastError());
   return EPPK_OK;
 }
@@ -2011,14 +1963,12 @@ int rows_check_fail(eppk_ctx* c, const char* who, uint32_t row) {
   return fail(c, EPPK_ERR_ARG, std::string(who ? who : "eppk_pick_batch") + ": request row " + std::to_string(row) + " out of range");
 }
 
-int row_check_ensure(eppk_ctx* c, uint32_t** h_bad, uint32_t** h_bad_dev, hipStream_t* st, hipEvent_t* ev) {
-  if (!*h_bad) {
-    HIPCHK(c, hipHostMalloc((void**)h_bad, 64, hipHostMallocDefault));
-    HIPCHK(c, hipHostGetDevicePointer((void**)h_bad_dev, *h_bad, 0));
-    **h_bad = 0xFFFFFFFFu;
-    HIPCHK(c, hipStreamCreateWithFlags(st, hipStreamNonBlocking));
-    HIPCHK(c, hipEventCreateWithFlags(ev, hipEventDisableTiming));
-  }
+int row_check_ensure(eppk_ctx* c, HBuf<uint32_t>& h_bad, hipStream_t* st, hipEvent_t* ev) {      // (each made once: a call that failed half-way is resumed)
+  bool fresh = false;
+  { const int rcg = ctx_grow(c, 16u, {{h_bad, 4u, "row-check word"}}, &fresh); if (rcg) return rcg; }
+  if (fresh) *h_bad = 0xFFFFFFFFu;
+  if (!*st) HIPCHK(c, hipStreamCreateWithFlags(st, hipStreamNonBlocking));
+  if (!*ev) HIPCHK(c, hipEventCreateWithFlags(ev, hipEventDisableTiming));
   return EPPK_OK;
 }
 
@@ -2032,28 +1982,23 @@ int validate_rows(eppk_ctx* c, const char* who, const void* reqs, uint32_t n_req
   return EPPK_OK;
 }
 
-int ensure_host_staging(eppk_ctx* c, bool need_mask) {
+// One set of staging buffers for max_batch rows, pinned and on the device (the context's own and those of its two StageSets), each group made
+// once.  The pinned ones carry what the device calls the same memory (.dev()): the zero-copy path of small batches hands that to the kernel.
+int staging_ensure(eppk_ctx* c, bool need_mask, HBuf<void>& h_reqs, HBuf<uint64_t>& h_mask, HBuf<int32_t>& h_pick, HBuf<double>& h_score,
+                   DBuf<void>& d_reqs, DBuf<uint64_t>& d_mask, DBuf<int32_t>& d_pick, DBuf<double>& d_score) {
   const size_t mb = c->cfg.max_batch;
-  if (!c->d_reqs) {
-    HIPCHK(c, hipMalloc(&c->d_reqs, mb * c->stride));
-    HIPCHK(c, hipMalloc((void**)&c->d_pick, (mb + EPPK_GROUP_MAX_DEVICES) * 4u));   // (+ the padding of a group's in-place all-gather)
-    HIPCHK(c, hipMalloc((void**)&c->d_score, mb * 8u));
-    HIPCHK(c, hipHostMalloc(&c->h_reqs, mb * c->stride, hipHostMallocDefault));
-    HIPCHK(c, hipHostMalloc((void**)&c->h_pick, mb * 4u, hipHostMallocDefault));
-    HIPCHK(c, hipHostMalloc((void**)&c->h_score, mb * 8u, hipHostMallocDefault));
-    // (what the device calls the same memory: the zero-copy path of small batches hands these to the kernel)
-    HIPCHK(c, hipHostGetDevicePointer(&c->h_reqs_dev, c->h_reqs, 0));
-    HIPCHK(c, hipHostGetDevicePointer((void**)&c->h_pick_dev, c->h_pick, 0));
-    HIPCHK(c, hipHostGetDevicePointer((void**)&c->h_score_dev, c->h_score, 0));
-    c->res_args_dirty = true;                // (the resident kernels' argument blocks name these buffers)
-  }
-  if (need_mask && !c->d_mask) {
-    HIPCHK(c, hipMalloc((void**)&c->d_mask, mb * c->jmax * 8u));
-    HIPCHK(c, hipHostMalloc((void**)&c->h_mask, mb * c->jmax * 8u, hipHostMallocDefault));
-    HIPCHK(c, hipHostGetDevicePointer((void**)&c->h_mask_dev, c->h_mask, 0));
-    c->res_args_dirty = true;
-  }
-  return EPPK_OK;
+  bool fresh = false, fresh_mask = false;
+  // (d_pick in 4-byte units: max_batch + the padding of a group's in-place all-gather, hence a group of its own)
+  int rc = ctx_grow(c, mb, {{d_reqs, c->stride, "staged rows"}, {d_score, 8u, "staged scores"}, {h_reqs, c->stride, "staged rows (pinned)"},
+                            {h_pick, 4u, "staged picks (pinned)"}, {h_score, 8u, "staged scores (pinned)"}}, &fresh);
+  if (!rc) rc = ctx_grow(c, mb + EPPK_GROUP_MAX_DEVICES, {{d_pick, 4u, "staged picks"}});
+  if (!rc && need_mask) rc = ctx_grow(c, mb, {{d_mask, c->jmax * 8u, "staged masks"}, {h_mask, c->jmax * 8u, "staged masks (pinned)"}}, &fresh_mask);
+  if (fresh || fresh_mask) c->res_args_dirty = true;        // (the resident kernels' argument blocks name these buffers)
+  return rc;
+}
+
+int ensure_host_staging(eppk_ctx* c, bool need_mask) {
+  return staging_ensure(c, need_mask, c->h_reqs, c->h_mask, c->h_pick, c->h_score, c->d_reqs, c->d_mask, c->d_pick, c->d_score);
 }
 
 // rows [lo, lo + n) of a batch of `full_n` rows starting at `base` (host memory; `pinned` = the device may DMA from it directly).
@@ -2077,12 +2022,12 @@ int pick_host_begin(eppk_ctx* c, const uint8_t* base, bool pinned, uint32_t full
     if (validate_as && !dev_check) { rc = validate_rows(c, validate_as, c->h_reqs, n, 0u); if (rc) return rc; }
     const bool use_mask = cand_mask_shard != nullptr && J != 0;
     if (use_mask && cand_mask_shard != c->h_mask) std::memcpy(c->h_mask, cand_mask_shard, (size_t)n * J * 8u);
-    rc = run_pick(c, (const uint8_t*)c->h_reqs_dev, n, use_mask ? c->h_mask_dev : nullptr, c->h_pick_dev, c->h_score_dev, c->stream, 1u, false, 0ull, 0u);
+    rc = run_pick(c, (const uint8_t*)c->h_reqs.dev(), n, use_mask ? c->h_mask.dev() : nullptr, c->h_pick.dev(), c->h_score.dev(), c->stream, 1u, false, 0ull, 0u);
     if (rc) return rc;
     if (dev_check) {        // beside the pick, on a stream of its own (it reads the row headers over PCIe as the pick does the rows)
-      rc = row_check_ensure(c, &c->check.h_bad, &c->check.h_bad_dev, &c->check.st, &c->check.done);
+      rc = row_check_ensure(c, c->check.h_bad, &c->check.st, &c->check.done);
       if (rc) return rc;
-      rc = rows_check_launch(c, c->h_reqs_dev, n, c->check.h_bad, c->check.h_bad_dev, c->check.st);
+      rc = rows_check_launch(c, c->h_reqs.dev(), n, c->check.h_bad, c->check.st);
       if (rc) return rc;
       HIPCHK(c, hipEventRecord(c->check.done, c->check.st));
       c->check.pending = true; c->check.side = true; c->check.who = validate_as;
@@ -2098,9 +2043,9 @@ int pick_host_begin(eppk_ctx* c, const uint8_t* base, bool pinned, uint32_t full
       // PCIe time of 0.31.)
       HIPCHK(c, hipMemcpyAsync(c->d_reqs, src, (size_t)up_n * c->stride, hipMemcpyHostToDevice, c->stream));
       if (validate_as) {    // on the device, behind the upload and in front of the pick (4 MB of headers out of HBM: microseconds)
-        rc = row_check_ensure(c, &c->check.h_bad, &c->check.h_bad_dev, &c->check.st, &c->check.done);
+        rc = row_check_ensure(c, c->check.h_bad, &c->check.st, &c->check.done);
         if (rc) return rc;
-        rc = rows_check_launch(c, c->d_reqs, up_n, c->check.h_bad, c->check.h_bad_dev, c->stream);
+        rc = rows_check_launch(c, c->d_reqs, up_n, c->check.h_bad, c->stream);
         if (rc) return rc;
         c->check.pending = true; c->check.side = false; c->check.who = validate_as;
       }
@@ -2121,9 +2066,9 @@ int pick_host_begin(eppk_ctx* c, const uint8_t* base, bool pinned, uint32_t full
         HIPCHK(c, hipMemcpyAsync((uint8_t*)c->d_reqs + off, from, len, hipMemcpyHostToDevice, c->stream));
       }
       if (validate_as) {    // the row headers: on the device, behind the last chunk (the host loop was a third of this path's time)
-        rc = row_check_ensure(c, &c->check.h_bad, &c->check.h_bad_dev, &c->check.st, &c->check.done);
+        rc = row_check_ensure(c, c->check.h_bad, &c->check.st, &c->check.done);
         if (rc) return rc;
-        rc = rows_check_launch(c, c->d_reqs, up_n, c->check.h_bad, c->check.h_bad_dev, c->stream);
+        rc = rows_check_launch(c, c->d_reqs, up_n, c->check.h_bad, c->stream);
         if (rc) return rc;
         c->check.pending = true; c->check.side = false; c->check.who = validate_as;
       }
@@ -2147,8 +2092,8 @@ int pick_host_begin(eppk_ctx* c, const uint8_t* base, bool pinned, uint32_t full
   // writes: 12 bytes per request) -- no download copies, two enqueues and two engine hand-offs less per batch; a group member keeps
   // its picks on the device (the gather reads them there).
   const bool host_out = allow_zero_copy && !upload_all;
-  rc = run_pick(c, d_shard, n, ((cand_mask_shard || mask_on_device) && J) ? c->d_mask : nullptr, host_out ? c->h_pick_dev : c->d_pick + (upload_all ? lo : 0u),
-                host_out ? c->h_score_dev : c->d_score + (upload_all ? lo : 0u), c->stream, 1u, false, 0ull, 0u);
+  rc = run_pick(c, d_shard, n, ((cand_mask_shard || mask_on_device) && J) ? c->d_mask : nullptr, host_out ? c->h_pick.dev() : c->d_pick + (upload_all ? lo : 0u),
+                host_out ? c->h_score.dev() : c->d_score + (upload_all ? lo : 0u), c->stream, 1u, false, 0ull, 0u);
   if (rc) return rc;
   if (!host_out) {
     HIPCHK(c, hipMemcpyAsync(c->h_pick, c->d_pick + (upload_all ? lo : 0u), (size_t)n * 4u, hipMemcpyDeviceToHost, c->stream));
@@ -2224,27 +2169,9 @@ int eppk_pick_batch_staged(eppk_ctx* c, uint32_t n_reqs, int use_mask, int32_t* 
 namespace {
 int stage_ensure(eppk_ctx* c, uint32_t set, bool need_mask) {
   eppk_ctx::StageSet& s = c->stage[set];
-  const size_t mb = c->cfg.max_batch;
-  if (!s.st) {
-    HIPCHK(c, hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
-    HIPCHK(c, hipEventCreateWithFlags(&s.picked, hipEventDisableTiming));
-    HIPCHK(c, hipMalloc(&s.d_reqs, mb * c->stride));
-    HIPCHK(c, hipMalloc((void**)&s.d_pick, (mb + EPPK_GROUP_MAX_DEVICES) * 4u));   // (+ the padding of a group's in-place all-gather)
-    HIPCHK(c, hipMalloc((void**)&s.d_score, mb * 8u));
-    HIPCHK(c, hipHostMalloc(&s.h_reqs, mb * c->stride, hipHostMallocDefault));
-    HIPCHK(c, hipHostMalloc((void**)&s.h_pick, mb * 4u, hipHostMallocDefault));
-    HIPCHK(c, hipHostMalloc((void**)&s.h_score, mb * 8u, hipHostMallocDefault));
-    HIPCHK(c, hipHostGetDevicePointer(&s.h_reqs_dev, s.h_reqs, 0));
-    HIPCHK(c, hipHostGetDevicePointer((void**)&s.h_pick_dev, s.h_pick, 0));
-    HIPCHK(c, hipHostGetDevicePointer((void**)&s.h_score_dev, s.h_score, 0));
-    c->res_args_dirty = true;                // (the resident kernels' argument blocks name these buffers)
-  }
-  if (need_mask && !s.d_mask) {
-    HIPCHK(c, hipMalloc((void**)&s.d_mask, mb * c->jmax * 8u));
-    HIPCHK(c, hipHostMalloc((void**)&s.h_mask, mb * c->jmax * 8u, hipHostMallocDefault));
-    HIPCHK(c, hipHostGetDevicePointer((void**)&s.h_mask_dev, s.h_mask, 0));
-    c->res_args_dirty = true;
-  }
+  if (!s.st) HIPCHK(c, hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));      // (each made once: a call that failed half-way is resumed)
+  if (!s.picked) HIPCHK(c, hipEventCreateWithFlags(&s.picked, hipEventDisableTiming));
+  { const int rcs = staging_ensure(c, need_mask, s.h_reqs, s.h_mask, s.h_pick, s.h_score, s.d_reqs, s.d_mask, s.d_pick, s.d_score); if (rcs) return rcs; }
   if (!c->learned) HIPCHK(c, hipEventCreateWithFlags(&c->learned, hipEventDisableTiming));
   return EPPK_OK;
 }
@@ -2307,10 +2234,10 @@ int eppk_pick_stage_begin(eppk_ctx* c, uint32_t set, uint32_t n_reqs, int use_ma
     // reads a DEVICE copy of the rows, uploaded on a stream of its own beside the pick (_end waits for that upload too), and the picks
     // out of the pinned result buffer (which only this set's next pick writes, and that one is ordered behind the update).
     const bool dev_check = n_reqs > c->host_check_max;
-    rc = dev_check ? row_check_ensure(c, &s.h_bad, &s.h_bad_dev, &s.st_check, &s.checked) : validate_rows(c, "eppk_pick_stage_begin", s.h_reqs, n_reqs, 0u);
+    rc = dev_check ? row_check_ensure(c, s.h_bad, &s.st_check, &s.checked) : validate_rows(c, "eppk_pick_stage_begin", s.h_reqs, n_reqs, 0u);
     if (rc) return rc;
     if (dev_check) {        // beside the pick, on a stream of its own (eppk_ctx::RowCheck)
-      rc = rows_check_launch(c, s.h_reqs_dev, n_reqs, s.h_bad, s.h_bad_dev, s.st_check);
+      rc = rows_check_launch(c, s.h_reqs.dev(), n_reqs, s.h_bad, s.st_check);
       if (rc) return rc;
       HIPCHK(c, hipEventRecord(s.checked, s.st_check));
       s.check_pending = true; s.check_side = true;
@@ -2327,7 +2254,7 @@ int eppk_pick_stage_begin(eppk_ctx* c, uint32_t set, uint32_t n_reqs, int use_ma
       s.copy_pending = true;
     }
     if (learn) { rc = learn_words_fence(c, s.st); if (rc) return rc; }
-    rc = run_pick(c, (const uint8_t*)s.h_reqs_dev, n_reqs, (use_mask && J) ? s.h_mask_dev : nullptr, s.h_pick_dev, s.h_score_dev, s.st, 1u, false, 0ull, 0u,
+    rc = run_pick(c, (const uint8_t*)s.h_reqs.dev(), n_reqs, (use_mask && J) ? s.h_mask.dev() : nullptr, s.h_pick.dev(), s.h_score.dev(), s.st, 1u, false, 0ull, 0u,
                   learn ? c->d_learn : nullptr, &words);
     if (rc) return rc;
     HIPCHK(c, hipEventRecord(s.picked, s.st));
@@ -2335,8 +2262,8 @@ int eppk_pick_stage_begin(eppk_ctx* c, uint32_t set, uint32_t n_reqs, int use_ma
   } else {
     // one upload, its row headers checked on the device (as eppk_pick_batch_staged does: eppk_ctx::RowCheck)
     HIPCHK(c, hipMemcpyAsync(s.d_reqs, s.h_reqs, (size_t)n_reqs * c->stride, hipMemcpyHostToDevice, s.st));
-    rc = row_check_ensure(c, &s.h_bad, &s.h_bad_dev, &s.st_check, &s.checked);
-    if (!rc) rc = rows_check_launch(c, s.d_reqs, n_reqs, s.h_bad, s.h_bad_dev, s.st);      // behind the upload, in front of the pick
+    rc = row_check_ensure(c, s.h_bad, &s.st_check, &s.checked);
+    if (!rc) rc = rows_check_launch(c, s.d_reqs, n_reqs, s.h_bad, s.st);      // behind the upload, in front of the pick
     if (rc) return rc;
     s.check_pending = true; s.check_side = false;
     if (use_mask && J) HIPCHK(c, hipMemcpyAsync(s.d_mask, s.h_mask, (size_t)n_reqs * J * 8u, hipMemcpyHostToDevice, s.st));
@@ -2344,7 +2271,7 @@ int eppk_pick_stage_begin(eppk_ctx* c, uint32_t set, uint32_t n_reqs, int use_ma
     // Picks and scores: written by the kernel straight into the set's pinned result buffers -- no download copies; a LEARN update reads
     // the picks from there, and only this set's next pick, ordered behind that update, writes them again.
     if (learn) { rc = learn_words_fence(c, s.st); if (rc) return rc; }
-    rc = run_pick(c, (const uint8_t*)s.d_reqs, n_reqs, (use_mask && J) ? s.d_mask : nullptr, s.h_pick_dev, s.h_score_dev, s.st, 1u, false, 0ull, 0u,
+    rc = run_pick(c, (const uint8_t*)s.d_reqs, n_reqs, (use_mask && J) ? s.d_mask : nullptr, s.h_pick.dev(), s.h_score.dev(), s.st, 1u, false, 0ull, 0u,
                   learn ? c->d_learn : nullptr, &words);
     if (rc) return rc;
     HIPCHK(c, hipEventRecord(s.picked, s.st));
@@ -2352,7 +2279,7 @@ int eppk_pick_stage_begin(eppk_ctx* c, uint32_t set, uint32_t n_reqs, int use_ma
   abort_guard.armed = false;                 // the picks are on their way: from here on the call succeeds and end() delivers them
   if (learn) {
     // the post-route update, chained on the device: rows and picks are there already (eppk_pick_learn_device's second half)
-    rc = learn_picks(c, s.d_reqs, s.h_pick_dev, n_reqs, s.st, words ? c->d_learn : nullptr);
+    rc = learn_picks(c, s.d_reqs, s.h_pick.dev(), n_reqs, s.st, words ? c->d_learn : nullptr);
     if (rc == EPPK_OK && hipEventRecord(c->learned, s.st) == hipSuccess) c->learn_pending = true;
     else c->host_flags |= EPPK_LAUNCH_LEARN_FAILED;        // (eppk_last_error holds the reason; the picks stand)
   }
@@ -2463,12 +2390,12 @@ int eppk_snapshot_set_addresses(eppk_ctx* c, const char* const* addrs, const cha
   if (!c->have_snapshot) return fail(c, EPPK_ERR_NO_SNAPSHOT, "eppk_snapshot_set_addresses: no snapshot published");
   if (n_pods != c->n_pods) return fail(c, EPPK_ERR_ARG, "eppk_snapshot_set_addresses: n_pods differs from the published snapshot");
   HIPCHK(c, hipSetDevice(c->cfg.device));
-  if (!c->d_at) {
+  {
     uint32_t t = 64;
     while (t < 8u * c->cfg.max_pods) t *= 2u;                      // two entries per pod, at most a quarter full
     c->at_slots = t;
-    HIPCHK(c, hipMalloc((void**)&c->d_at, (size_t)t * 16u));
-    HIPCHK(c, hipMalloc((void**)&c->d_av, (size_t)t * 4u));
+    const int rcg = ctx_grow(c, t, {{c->d_at, 16u, "address fingerprints"}, {c->d_av, 4u, "address pods"}});
+    if (rcg) return rcg;
   }
   const uint32_t T = c->at_slots;
   std::vector<uint64_t> at((size_t)T * 2u, 0ull);
@@ -2519,16 +2446,14 @@ int stage_subset_entries(eppk_ctx* c, const char* who, const uint64_t* keys, con
     if (off[r + 1] < off[r]) return fail(c, EPPK_ERR_ARG, std::string(who) + ": off[] must be non-decreasing");
   const size_t n_keys = off[n_reqs];
   if (n_keys && !keys) return fail(c, EPPK_ERR_ARG, std::string(who) + ": null keys");
-  if (n_keys > c->sk_cap) {
-    (void)hipFree(c->d_sk); c->d_sk = nullptr; c->sk_cap = 0;
+  if (n_keys > c->d_sk.cap()) {
     size_t cap = 1024; while (cap < n_keys) cap *= 2;
-    HIPCHK(c, hipMalloc((void**)&c->d_sk, cap * 16u));
-    c->sk_cap = cap;
+    const int rcg = ctx_grow(c, cap, {{c->d_sk, 16u, "subset keys"}});
+    if (rcg) return rcg;
   }
-  if ((size_t)n_reqs + 1u > c->so_cap) {
-    (void)hipFree(c->d_so); c->d_so = nullptr; c->so_cap = 0;
-    HIPCHK(c, hipMalloc((void**)&c->d_so, ((size_t)c->cfg.max_batch + 1u) * 4u));
-    c->so_cap = (size_t)c->cfg.max_batch + 1u;
+  if ((size_t)n_reqs + 1u > c->d_so.cap()) {
+    const int rcg = ctx_grow(c, (size_t)c->cfg.max_batch + 1u, {{c->d_so, 4u, "subset offsets"}});
+    if (rcg) return rcg;
   }
   if (n_keys) HIPCHK(c, hipMemcpyAsync(c->d_sk, keys, n_keys * 16u, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_so, off, ((size_t)n_reqs + 1u) * 4u, hipMemcpyHostToDevice, c->stream));
@@ -2593,13 +2518,8 @@ int eppk_pick_batch_subset(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const
 namespace {
 int topk_ensure(eppk_ctx* c, bool need_mask) {
   const size_t mb = c->cfg.max_batch;
-  if (!c->d_tk_reqs) {
-    HIPCHK(c, hipMalloc(&c->d_tk_reqs, mb * c->stride));
-    HIPCHK(c, hipMalloc((void**)&c->d_tk_pick, mb * EPPK_MAX_TOPK * 4u));
-    HIPCHK(c, hipMalloc((void**)&c->d_tk_score, mb * EPPK_MAX_TOPK * 8u));
-  }
-  if (need_mask && !c->d_tk_mask) HIPCHK(c, hipMalloc((void**)&c->d_tk_mask, mb * c->jmax * 8u));
-  return EPPK_OK;
+  const int rc = ctx_grow(c, mb, {{c->d_tk_reqs, c->stride, "top-k rows"}, {c->d_tk_pick, EPPK_MAX_TOPK * 4u, "top-k picks"}, {c->d_tk_score, EPPK_MAX_TOPK * 8u, "top-k scores"}});
+  return rc || !need_mask ? rc : ctx_grow(c, mb, {{c->d_tk_mask, c->jmax * 8u, "top-k masks"}});
 }
 }  // namespace
 
@@ -2652,7 +2572,7 @@ int eppk_pick_topk(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint64_
     if (cand_mask && cand_mask != c->h_mask) std::memcpy(c->h_mask, cand_mask, (size_t)n_reqs * J * 8u);
     // the latency path of a dispatcher that asks for fallback lists (every one of its batches comes through here): a resident workgroup
     if (resident_takes(c, n_reqs, cand_mask != nullptr, k)) return resident_pick(c, n_reqs, out_pick, out_score, "eppk_pick_topk", cand_mask != nullptr, k);
-    rc = run_pick(c, (const uint8_t*)c->h_reqs_dev, n_reqs, cand_mask ? c->h_mask_dev : nullptr, c->h_pick_dev, c->h_score_dev, c->stream, k, false, 0ull, 0u);
+    rc = run_pick(c, (const uint8_t*)c->h_reqs.dev(), n_reqs, cand_mask ? c->h_mask.dev() : nullptr, c->h_pick.dev(), c->h_score.dev(), c->stream, k, false, 0ull, 0u);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::memcpy(out_pick, c->h_pick, (size_t)n_reqs * k * 4u);
@@ -2705,12 +2625,12 @@ int eppk_pick_random_topk(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const 
   if (reqs != c->h_reqs) std::memcpy(c->h_reqs, reqs, (size_t)n_reqs * c->stride);
   if (cand_mask && cand_mask != c->h_mask) std::memcpy(c->h_mask, cand_mask, (size_t)n_reqs * J * 8u);
   if (n_reqs <= c->zero_copy_max) {          // zero-copy (small batch): the kernels read the pinned rows and write the pinned results
-    rc = run_pick(c, (const uint8_t*)c->h_reqs_dev, n_reqs, cand_mask ? c->h_mask_dev : nullptr, c->h_pick_dev, c->h_score_dev, c->stream, k, true, seed, 0u);
+    rc = run_pick(c, (const uint8_t*)c->h_reqs.dev(), n_reqs, cand_mask ? c->h_mask.dev() : nullptr, c->h_pick.dev(), c->h_score.dev(), c->stream, k, true, seed, 0u);
     if (rc) return rc;
   } else {                                   // one upload; the results still land in the pinned buffers (no download copies)
     HIPCHK(c, hipMemcpyAsync(c->d_reqs, c->h_reqs, (size_t)n_reqs * c->stride, hipMemcpyHostToDevice, c->stream));
     if (cand_mask) HIPCHK(c, hipMemcpyAsync(c->d_mask, c->h_mask, (size_t)n_reqs * J * 8u, hipMemcpyHostToDevice, c->stream));
-    rc = run_pick(c, (const uint8_t*)c->d_reqs, n_reqs, cand_mask ? c->d_mask : nullptr, c->h_pick_dev, c->h_score_dev, c->stream, k, true, seed, 0u);
+    rc = run_pick(c, (const uint8_t*)c->d_reqs, n_reqs, cand_mask ? c->d_mask : nullptr, c->h_pick.dev(), c->h_score.dev(), c->stream, k, true, seed, 0u);
     if (rc) return rc;
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2754,7 +2674,7 @@ int eppk_pick_weighted_random(eppk_ctx* c, const void* reqs, uint32_t n_reqs, co
     if (rc) return rc;
     if (reqs != c->h_reqs) std::memcpy(c->h_reqs, reqs, (size_t)n_reqs * c->stride);
     if (cand_mask && cand_mask != c->h_mask) std::memcpy(c->h_mask, cand_mask, (size_t)n_reqs * J * 8u);
-    rc = run_pick(c, (const uint8_t*)c->h_reqs_dev, n_reqs, cand_mask ? c->h_mask_dev : nullptr, c->h_pick_dev, c->h_score_dev, c->stream, k, false, seed, 0u,
+    rc = run_pick(c, (const uint8_t*)c->h_reqs.dev(), n_reqs, cand_mask ? c->h_mask.dev() : nullptr, c->h_pick.dev(), c->h_score.dev(), c->stream, k, false, seed, 0u,
                   nullptr, nullptr, true);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2818,8 +2738,9 @@ int eppk_set_filters(eppk_ctx* c, const eppk_filter_program* progs, uint32_t n_p
 namespace {
 // The planes as of the current rows and programs, on `st` in front of the filter launch that reads them (see eppk_ctx::filt_gen).
 int filter_planes(eppk_ctx* c, hipStream_t st) {
-  if (!c->d_fplanes) {
-    HIPCHK(c, hipMalloc((void**)&c->d_fplanes, eppk::kFilterBufBytes));
+  bool fresh = false;
+  { const int rcg = ctx_grow(c, eppk::kFilterBufBytes, {{c->d_fplanes, 1u, "filter planes"}}, &fresh); if (rcg) return rcg; }
+  if (fresh) {
     HIPCHK(c, hipMemsetAsync(c->d_fplanes, 0, eppk::kFilterBufBytes, st));      // (on the stream of the build behind it: the context's stream does not wait for the null stream)
     c->filt_built = 0;
   }
@@ -2842,9 +2763,7 @@ int filter_cls_check(eppk_ctx* c, const char* who, const uint8_t* cls, uint32_t 
 
 int filter_host_buffers(eppk_ctx* c) {
   const size_t mb = c->cfg.max_batch ? c->cfg.max_batch : 1u;
-  if (!c->d_fcls) HIPCHK(c, hipMalloc((void**)&c->d_fcls, mb));
-  if (!c->d_fverdict) HIPCHK(c, hipMalloc((void**)&c->d_fverdict, mb));
-  return EPPK_OK;
+  return ctx_grow(c, mb, {{c->d_fcls, 1u, "filter classes"}, {c->d_fverdict, 1u, "filter verdicts"}});
 }
 }  // namespace
 
@@ -2905,14 +2824,9 @@ int eppk_pick_filtered_device(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, 
     if (d_out_verdict) HIPCHK(c, hipMemsetAsync(d_out_verdict, 0, n_reqs, st));
     return eppk_pick_topk_device(c, d_reqs, n_reqs, d_cand_mask, k, d_out_pick, d_out_score, stream);
   }
-  if (n_reqs > c->fmask_rows) {                   // (rare: the first call, or a larger batch than ever before)
-    { const int rcs = device_sync(c); if (rcs) return rcs; }
-    (void)hipFree(c->d_fmask); c->d_fmask = nullptr; c->fmask_rows = 0;
-    const size_t rows = n_reqs > c->cfg.max_batch ? n_reqs : c->cfg.max_batch;
-    HIPCHK(c, hipMalloc((void**)&c->d_fmask, rows * (c->jmax ? c->jmax : 1u) * 8u));
-    c->fmask_rows = rows;
-  }
-  int rc = eppk_filter_masks_device(c, d_reqs, n_reqs, d_cls, d_cand_mask, c->d_fmask, d_out_verdict, stream);
+  int rc = ctx_grow(c, n_reqs > c->cfg.max_batch ? n_reqs : c->cfg.max_batch, {{c->d_fmask, (c->jmax ? c->jmax : 1u) * 8u, "filter mask rows"}});
+  if (rc) return rc;
+  rc = eppk_filter_masks_device(c, d_reqs, n_reqs, d_cls, d_cand_mask, c->d_fmask, d_out_verdict, stream);
   if (rc) return rc;
   // (a snapshot without pods has no mask words: the caller's own mask pointer, which the pick treats as it always has)
   return eppk_pick_topk_device(c, d_reqs, n_reqs, c->n_pods ? c->d_fmask : d_cand_mask, k, d_out_pick, d_out_score, stream);
@@ -2964,30 +2878,11 @@ int eppk_pick_filtered(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uin
 
 namespace {
 
-// Scratch buffers of the bounded picker that share one capacity (`*have`, in units) and have to hold `need` units: kept when they do,
-// else replaced together (rare: the first call, or a larger batch than ever before; what is queued may still read the old ones, so the
-// device is drained first -- include/eppk.h says so).
-struct BoundBuf { void** p; size_t unit_bytes; };
-int bounded_grow(eppk_ctx* c, size_t* have, size_t need, std::initializer_list<BoundBuf> bufs) {
-  if (need <= *have && *have) return EPPK_OK;
-  { const int rcs = device_sync(c); if (rcs) return rcs; }
-  *have = 0;
-  for (const BoundBuf& b : bufs) { (void)hipFree(*b.p); *b.p = nullptr; }
-  for (const BoundBuf& b : bufs)
-    if (hipMalloc(b.p, (need ? need : 1u) * b.unit_bytes) != hipSuccess) {
-      (void)hipGetLastError(); *b.p = nullptr;
-      for (const BoundBuf& f : bufs) { (void)hipFree(*f.p); *f.p = nullptr; }
-      return fail(c, EPPK_ERR_NOMEM, "bounded picker: scratch of " + std::to_string(need * b.unit_bytes) + " bytes");
-    }
-  *have = need ? need : 1u;
-  return EPPK_OK;
-}
 // rows of a per-request buffer: the context's max_batch, or the batch when a *_device caller hands over more
 size_t bounded_rows(const eppk_ctx* c, uint32_t n_reqs) { return n_reqs > c->cfg.max_batch ? (size_t)n_reqs : (size_t)c->cfg.max_batch; }
 
 int bounded_pod_scratch(eppk_ctx* c) {
-  if (!c->d_bd_pods) HIPCHK(c, hipMalloc((void**)&c->d_bd_pods, 4u * EPPK_MAX_PODS * sizeof(uint32_t)));
-  return EPPK_OK;
+  return ctx_grow(c, 4u * EPPK_MAX_PODS, {{c->d_bd_pods, sizeof(uint32_t), "bounded picker: pod scratch"}});
 }
 
 int bounded_check(eppk_ctx* c, const char* who, uint32_t k, uint32_t policy) {
@@ -3005,7 +2900,7 @@ int bounded_resolve(eppk_ctx* c, const int32_t* d_lists, const double* d_scores,
   const uint32_t P = c->n_pods, chunk = c->bound_chunk;
   uint8_t* state = d_out_rank;
   if (!state) {
-    const int rc = bounded_grow(c, &c->bd_state_rows, bounded_rows(c, n_reqs), {{(void**)&c->d_bd_state, 1u}});
+    const int rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_bd_state, 1u, "bounded picker: request states"}});
     if (rc) return rc;
     state = c->d_bd_state;
   }
@@ -3018,7 +2913,7 @@ int bounded_resolve(eppk_ctx* c, const int32_t* d_lists, const double* d_scores,
   const uint32_t n_chunks = (uint32_t)(((uint64_t)n_reqs + chunk - 1u) / chunk);
   int rc = bounded_pod_scratch(c);
   if (rc) return rc;
-  if ((rc = bounded_grow(c, &c->bd_hist_words, (size_t)n_chunks * P, {{(void**)&c->d_bd_hist, sizeof(uint32_t)}}))) return rc;
+  if ((rc = ctx_grow(c, (size_t)n_chunks * P, {{c->d_bd_hist, sizeof(uint32_t), "bounded picker: bid histogram"}}))) return rc;
   uint32_t* room = c->d_bd_pods;
   uint32_t* load = d_load;
   if (!load) {
@@ -3051,8 +2946,8 @@ int bounded_host_around(eppk_ctx* c, uint32_t n_reqs, const uint32_t* cap, uint3
                         const BoundResolveFn& resolve) {
   int rc = bounded_pod_scratch(c);
   if (rc) return rc;
-  if ((rc = bounded_grow(c, &c->bd_out_rows, bounded_rows(c, n_reqs),
-                         {{(void**)&c->d_bd_opick, 4u}, {(void**)&c->d_bd_oscore, 8u}, {(void**)&c->d_bd_orank, 1u}}))) return rc;
+  if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_bd_opick, 4u, "bounded picker: picks"}, {c->d_bd_oscore, 8u, "bounded picker: scores"},
+                                                  {c->d_bd_orank, 1u, "bounded picker: ranks"}}))) return rc;
   uint32_t* d_cap = c->d_bd_pods + 2u * EPPK_MAX_PODS;
   uint32_t* d_load = c->d_bd_pods + 3u * EPPK_MAX_PODS;
   const size_t pod_bytes = (size_t)c->n_pods * sizeof(uint32_t);
@@ -3077,8 +2972,7 @@ int bounded_host_finish(eppk_ctx* c, const int32_t* d_lists, const double* d_sco
 }
 
 int bounded_lists(eppk_ctx* c, uint32_t n_reqs) {
-  return bounded_grow(c, &c->bd_list_rows, bounded_rows(c, n_reqs),
-                      {{(void**)&c->d_bd_list, EPPK_MAX_TOPK * 4u}, {(void**)&c->d_bd_lscore, EPPK_MAX_TOPK * 8u}});
+  return ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_bd_list, EPPK_MAX_TOPK * 4u, "bounded picker: lists"}, {c->d_bd_lscore, EPPK_MAX_TOPK * 8u, "bounded picker: list scores"}});
 }
 
 }  // namespace
@@ -3195,7 +3089,7 @@ int banded_resolve(eppk_ctx* c, const int32_t* d_lists, const double* d_scores, 
   const uint32_t P = c->n_pods, chunk = c->bound_chunk;
   uint8_t* state = d_out_rank;
   if (!state) {
-    const int rc = bounded_grow(c, &c->bd_state_rows, bounded_rows(c, n_reqs), {{(void**)&c->d_bd_state, 1u}});
+    const int rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_bd_state, 1u, "bounded picker: request states"}});
     if (rc) return rc;
     state = c->d_bd_state;
   }
@@ -3208,9 +3102,9 @@ int banded_resolve(eppk_ctx* c, const int32_t* d_lists, const double* d_scores, 
   const uint32_t n_chunks = (uint32_t)(((uint64_t)n_reqs + chunk - 1u) / chunk);
   int rc = bounded_pod_scratch(c);
   if (rc) return rc;
-  if ((rc = bounded_grow(c, &c->bd_hist_words, (size_t)n_chunks * P, {{(void**)&c->d_bd_hist, sizeof(uint32_t)}}))) return rc;
-  if ((rc = bounded_grow(c, &c->bn_perm_rows, bounded_rows(c, n_reqs), {{(void**)&c->d_bn_perm, sizeof(uint32_t)}}))) return rc;
-  if ((rc = bounded_grow(c, &c->bn_bh_words, eppk::kBandSegWords + (size_t)n_chunks * EPPK_MAX_BANDS, {{(void**)&c->d_bn_bh, sizeof(uint32_t)}}))) return rc;
+  if ((rc = ctx_grow(c, (size_t)n_chunks * P, {{c->d_bd_hist, sizeof(uint32_t), "bounded picker: bid histogram"}}))) return rc;
+  if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_bn_perm, sizeof(uint32_t), "banded picker: band order"}}))) return rc;
+  if ((rc = ctx_grow(c, eppk::kBandSegWords + (size_t)n_chunks * EPPK_MAX_BANDS, {{c->d_bn_bh, sizeof(uint32_t), "banded picker: band histogram"}}))) return rc;
   uint32_t* seg = c->d_bn_bh;
   uint32_t* bh = c->d_bn_bh + eppk::kBandSegWords;
   uint32_t* perm = c->d_bn_perm;
@@ -3256,7 +3150,7 @@ int banded_host_finish(eppk_ctx* c, const int32_t* d_lists, const double* d_scor
                        const uint32_t* counts, const eppk::BandTab& tab, const uint32_t* cap, uint32_t cap_all, uint32_t* load, int32_t* out_pick,
                        double* out_score, uint8_t* out_rank) {
   if (band) {
-    const int rc = bounded_grow(c, &c->bn_band_rows, bounded_rows(c, n_reqs), {{(void**)&c->d_bn_band, 1u}});
+    const int rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_bn_band, 1u, "banded picker: bands"}});
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->d_bn_band, band, n_reqs, hipMemcpyHostToDevice, c->stream));
   }
@@ -3351,7 +3245,7 @@ int costed_resolve(eppk_ctx* c, const int32_t* d_lists, const double* d_scores, 
   const eppk::CostOf cost{d_cost, k, cost_flags & EPPK_COST_PER_ENTRY};
   uint8_t* state = d_out_rank;
   if (!state) {
-    const int rc = bounded_grow(c, &c->bd_state_rows, bounded_rows(c, n_reqs), {{(void**)&c->d_bd_state, 1u}});
+    const int rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_bd_state, 1u, "bounded picker: request states"}});
     if (rc) return rc;
     state = c->d_bd_state;
   }
@@ -3364,10 +3258,10 @@ int costed_resolve(eppk_ctx* c, const int32_t* d_lists, const double* d_scores, 
   const uint32_t n_chunks = (uint32_t)(((uint64_t)n_reqs + chunk - 1u) / chunk);
   int rc = bounded_pod_scratch(c);
   if (rc) return rc;
-  if ((rc = bounded_grow(c, &c->bd_hist_words, (size_t)n_chunks * P, {{(void**)&c->d_bd_hist, sizeof(uint32_t)}}))) return rc;
-  if ((rc = bounded_grow(c, &c->bn_perm_rows, bounded_rows(c, n_reqs), {{(void**)&c->d_bn_perm, sizeof(uint32_t)}}))) return rc;
-  if ((rc = bounded_grow(c, &c->bn_bh_words, eppk::kBandSegWords + (size_t)n_chunks * EPPK_MAX_BANDS, {{(void**)&c->d_bn_bh, sizeof(uint32_t)}}))) return rc;
-  if ((rc = bounded_grow(c, &c->cs_acc_words, (size_t)EPPK_MAX_PODS, {{(void**)&c->d_cs_acc, sizeof(uint32_t)}}))) return rc;
+  if ((rc = ctx_grow(c, (size_t)n_chunks * P, {{c->d_bd_hist, sizeof(uint32_t), "bounded picker: bid histogram"}}))) return rc;
+  if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_bn_perm, sizeof(uint32_t), "banded picker: band order"}}))) return rc;
+  if ((rc = ctx_grow(c, eppk::kBandSegWords + (size_t)n_chunks * EPPK_MAX_BANDS, {{c->d_bn_bh, sizeof(uint32_t), "banded picker: band histogram"}}))) return rc;
+  if ((rc = ctx_grow(c, (size_t)EPPK_MAX_PODS, {{c->d_cs_acc, sizeof(uint32_t), "costed picker: takers' totals"}}))) return rc;
   uint32_t* seg = c->d_bn_bh;
   uint32_t* bh = c->d_bn_bh + eppk::kBandSegWords;
   uint32_t* perm = c->d_bn_perm;
@@ -3417,10 +3311,10 @@ int costed_host_finish(eppk_ctx* c, const int32_t* d_lists, const double* d_scor
                        double* out_score, uint8_t* out_rank) {
   int rc;
   if (band) {
-    if ((rc = bounded_grow(c, &c->bn_band_rows, bounded_rows(c, n_reqs), {{(void**)&c->d_bn_band, 1u}}))) return rc;
+    if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_bn_band, 1u, "banded picker: bands"}}))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->d_bn_band, band, n_reqs, hipMemcpyHostToDevice, c->stream));
   }
-  if ((rc = bounded_grow(c, &c->cs_cost_rows, bounded_rows(c, n_reqs), {{(void**)&c->d_cs_cost, sizeof(uint32_t)}}))) return rc;
+  if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_cs_cost, sizeof(uint32_t), "costed picker: costs"}}))) return rc;
   HIPCHK(c, hipMemcpyAsync(c->d_cs_cost, cost, (size_t)n_reqs * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
   return bounded_host_around(c, n_reqs, cap, load, out_pick, out_score, out_rank,
                              [&](const uint32_t* d_cap, uint32_t* d_load, int32_t* d_pick, double* d_score, uint8_t* d_rank) {
@@ -3614,15 +3508,15 @@ struct eppk_group {
   uint32_t mode = 0;
   uint32_t min_shard = 2048;
   uint32_t max_batch = 0;
-  void* h_stage = nullptr; size_t h_stage_bytes = 0;   // ONE pinned, portable copy of a batch: every device DMAs from it
+  GBuf<void> h_stage;   // (capacity: bytes) ONE pinned, portable copy of a batch: every device DMAs from it
   std::vector<hipEvent_t> ev;                           // ev[g]: device g's shard of picks is in every peer's array (PEER)
   // ordered fallbacks over the group (eppk_group_pick_topk / _random_topk): pinned, portable mask and result staging
-  uint64_t* h_tk_mask = nullptr; int32_t* h_tk_pick = nullptr; double* h_tk_score = nullptr;
+  GBuf<uint64_t> h_tk_mask; GBuf<int32_t> h_tk_pick; GBuf<double> h_tk_score;
   // The PIPELINED host path over the group (eppk_group_pick_stage_*): per set ONE pinned, portable buffer of rows / masks / results that
   // the caller fills and every member's DMA engine reads; the members work on their own staging sets' streams and device buffers
   // (eppk_ctx::stage[set]).  sev[set][i]: member i's shard of picks has landed in every peer's array (PEER gather of a LEARN batch).
   struct GStage {
-    void* h_reqs = nullptr; uint64_t* h_mask = nullptr; int32_t* h_pick = nullptr; double* h_score = nullptr;
+    GBuf<void> h_reqs; GBuf<uint64_t> h_mask; GBuf<int32_t> h_pick; GBuf<double> h_score;
     uint32_t n = 0, used = 0, per = 0; bool busy = false, had_mask = false, learn = false, host_learn = false;
     std::vector<hipEvent_t> sev;
     std::vector<hipEvent_t> cev;   // cev[p]: member p's update has read its copy of this set's gathered picks: the peers may push the next batch's into it
@@ -3650,6 +3544,15 @@ int gfail(eppk_group* g, int code, const std::string& msg) {
   if (g) g->err = msg;
   else { std::lock_guard<std::mutex> l(g_err_mu); g_group_err = msg; }
   return code;
+}
+
+// eppk::grow for the group's pinned, portable buffers.  Each has one size for the life of the group (made once, never replaced); the
+// drain of a replacement would be every member's.
+int group_pinned(eppk_group* g, size_t need, std::initializer_list<eppk::Member> bufs) {
+  std::string what;
+  const int rc = eppk::grow([g] { for (eppk_ctx* m : g->ctx) { if (hipSetDevice(m->cfg.device) != hipSuccess) return (int)EPPK_ERR_DEVICE; const int rcs = device_sync(m); if (rcs) return rcs; } return (int)EPPK_OK; },
+                            need, bufs, nullptr, &what);
+  return rc ? gfail(g, rc, rc == EPPK_ERR_NOMEM ? what : "group staging: a member could not be drained") : rc;
 }
 
 int group_load_rccl(eppk_group* g) {
@@ -3751,17 +3654,9 @@ void eppk_group_destroy(eppk_group* g) {
   for (eppk_group::GStage& gs : g->gstage) {
     for (size_t i = 0; i < gs.sev.size(); ++i) { (void)hipSetDevice(g->dev[i]); (void)hipEventDestroy(gs.sev[i]); }
     for (size_t i = 0; i < gs.cev.size(); ++i) { (void)hipSetDevice(g->dev[i]); (void)hipEventDestroy(gs.cev[i]); }
-    if (gs.h_reqs) (void)hipHostFree(gs.h_reqs);
-    if (gs.h_mask) (void)hipHostFree(gs.h_mask);
-    if (gs.h_pick) (void)hipHostFree(gs.h_pick);
-    if (gs.h_score) (void)hipHostFree(gs.h_score);
   }
   for (eppk_ctx* m : g->ctx) eppk_destroy(m);
-  if (g->h_stage) (void)hipHostFree(g->h_stage);
-  if (g->h_tk_mask) (void)hipHostFree(g->h_tk_mask);
-  if (g->h_tk_pick) (void)hipHostFree(g->h_tk_pick);
-  if (g->h_tk_score) (void)hipHostFree(g->h_tk_score);
-  delete g;     // (librccl stays loaded: unloading a library that owns device state is not worth the risk)
+  delete g;     // (the members first, then the group's pinned buffers go with it; librccl stays loaded: unloading a library that owns device state is not worth the risk)
 }
 
 uint32_t eppk_group_size(const eppk_group* g) { return g ? (uint32_t)g->ctx.size() : 0u; }
@@ -3821,12 +3716,7 @@ int eppk_group_pick_batch(eppk_group* g, const void* reqs, uint32_t n_reqs, cons
   const size_t J = (c0->n_pods + 63u) / 64u;
   // ONE pinned + portable staging copy of the batch; every device's DMA engine reads it over its own PCIe link
   const size_t need = (size_t)g->max_batch * c0->stride;
-  if (g->h_stage_bytes < need) {
-    if (g->h_stage) (void)hipHostFree(g->h_stage);
-    g->h_stage = nullptr; g->h_stage_bytes = 0;
-    if (hipHostMalloc(&g->h_stage, need, hipHostMallocPortable) != hipSuccess) return gfail(g, EPPK_ERR_NOMEM, "eppk_group_pick_batch: pinned staging");
-    g->h_stage_bytes = need;
-  }
+  if ((rc = group_pinned(g, need, {{g->h_stage, 1u, "eppk_group_pick_batch: pinned staging"}}))) return rc;
   std::memcpy(g->h_stage, reqs, (size_t)n_reqs * c0->stride);
   auto lo_of = [&](uint32_t i) { const uint64_t l = (uint64_t)i * per; return (uint32_t)(l < n_reqs ? l : n_reqs); };
   auto cnt_of = [&](uint32_t i) { if (i >= used) return 0u; const uint32_t l = lo_of(i), h = lo_of(i + 1); return h - l; };
@@ -3977,12 +3867,6 @@ int eppk_group_index_trim_pods(eppk_group* g, uint32_t cap_per_pod, uint64_t* n_
 
 namespace {
 
-int group_pinned(eppk_group* g, void** p, size_t bytes, const char* what) {
-  if (*p) return EPPK_OK;
-  if (hipHostMalloc(p, bytes ? bytes : 8u, hipHostMallocPortable) != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return gfail(g, EPPK_ERR_NOMEM, std::string(what) + ": pinned staging"); }
-  return EPPK_OK;
-}
-
 // how a batch of n requests is spread over the members: `used` of them, `per` rows each (the last one what is left)
 struct Shards {
   uint32_t n, used, per;
@@ -4017,11 +3901,9 @@ int group_topk(eppk_group* g, const char* who, const void* reqs, uint32_t n_reqs
     return EPPK_OK;
   }
   const size_t mb = g->max_batch;
-  if ((rc = group_pinned(g, &g->h_stage, mb * c0->stride, who))) return rc;
-  g->h_stage_bytes = g->h_stage_bytes < mb * c0->stride ? mb * c0->stride : g->h_stage_bytes;
-  if ((rc = group_pinned(g, (void**)&g->h_tk_pick, mb * EPPK_MAX_TOPK * 4u, who))) return rc;
-  if ((rc = group_pinned(g, (void**)&g->h_tk_score, mb * EPPK_MAX_TOPK * 8u, who))) return rc;
-  if (cand_mask && (rc = group_pinned(g, (void**)&g->h_tk_mask, mb * c0->jmax * 8u, who))) return rc;
+  if ((rc = group_pinned(g, mb * c0->stride, {{g->h_stage, 1u, "pinned staging of a group batch"}}))) return rc;
+  if ((rc = group_pinned(g, mb, {{g->h_tk_pick, EPPK_MAX_TOPK * 4u, "pinned top-k picks of a group"}, {g->h_tk_score, EPPK_MAX_TOPK * 8u, "pinned top-k scores of a group"}}))) return rc;
+  if (cand_mask && (rc = group_pinned(g, mb, {{g->h_tk_mask, c0->jmax * 8u, "pinned top-k masks of a group"}}))) return rc;
   std::memcpy(g->h_stage, reqs, (size_t)n_reqs * c0->stride);
   if (cand_mask) std::memcpy(g->h_tk_mask, cand_mask, (size_t)n_reqs * J * 8u);
   const Shards sh(g, n_reqs);
@@ -4178,10 +4060,9 @@ int eppk_group_pick_stage_buffers(eppk_group* g, uint32_t set, void** reqs, uint
   eppk_ctx* c0 = g->ctx[0];
   const size_t mb = g->max_batch;
   int rc;
-  if ((rc = group_pinned(g, &gs.h_reqs, mb * c0->stride, "eppk_group_pick_stage_buffers"))) return rc;
-  if ((rc = group_pinned(g, (void**)&gs.h_pick, mb * 4u, "eppk_group_pick_stage_buffers"))) return rc;
-  if ((rc = group_pinned(g, (void**)&gs.h_score, mb * 8u, "eppk_group_pick_stage_buffers"))) return rc;
-  if (cand_mask && (rc = group_pinned(g, (void**)&gs.h_mask, mb * c0->jmax * 8u, "eppk_group_pick_stage_buffers"))) return rc;
+  if ((rc = group_pinned(g, mb, {{gs.h_reqs, c0->stride, "pinned rows of a group's staging set"}, {gs.h_pick, 4u, "pinned picks of a group's staging set"},
+                                 {gs.h_score, 8u, "pinned scores of a group's staging set"}}))) return rc;
+  if (cand_mask && (rc = group_pinned(g, mb, {{gs.h_mask, c0->jmax * 8u, "pinned masks of a group's staging set"}}))) return rc;
   if (gs.sev.empty()) {
     GFOR(g, i) {
       hipEvent_t e;
@@ -4249,8 +4130,8 @@ int eppk_group_pick_stage_begin(eppk_group* g, uint32_t set, uint32_t n_reqs, in
     const uint32_t up_lo = learn ? 0u : lo, up_n = learn ? n_reqs : cnt;
     if (hipMemcpyAsync(s.d_reqs, (const uint8_t*)gs.h_reqs + (size_t)up_lo * m->stride, (size_t)up_n * m->stride, hipMemcpyHostToDevice, s.st) != hipSuccess)
       return gfail(g, EPPK_ERR_DEVICE, "eppk_group_pick_stage_begin: upload failed");
-    int rc = row_check_ensure(m, &s.h_bad, &s.h_bad_dev, &s.st_check, &s.checked);
-    if (!rc) rc = rows_check_launch(m, s.d_reqs, up_n, s.h_bad, s.h_bad_dev, s.st);
+    int rc = row_check_ensure(m, s.h_bad, &s.st_check, &s.checked);
+    if (!rc) rc = rows_check_launch(m, s.d_reqs, up_n, s.h_bad, s.st);
     if (rc) return mfail(rc);
     s.check_pending = true; s.check_side = false; s.row_base = up_lo;
     if (cnt) {

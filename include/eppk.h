@@ -56,7 +56,10 @@ typedef enum eppk_status {
   EPPK_ERR_DEVICE      = -3, /* HIP runtime error (message in eppk_last_error)               */
   EPPK_ERR_NO_SNAPSHOT = -4, /* pick before the first eppk_snapshot_publish                  */
   EPPK_ERR_INDEX_FULL  = -5, /* prefix table load factor exceeded; grow index_slots          */
-  EPPK_ERR_NOMEM       = -6
+  EPPK_ERR_NOMEM       = -6  /* an allocation failed (eppk_last_error names the buffer and the bytes).  Whichever entry point
+                                reports it, no group of buffers is left half-made (buffers that are sized together are made
+                                together or not at all; a group that could not be replaced is empty and is made again by the
+                                next call that needs it), and the call may be repeated                                        */
 } eppk_status;
 
 /* Scorer plugins of the fused chain.  Replaces Scorer.Score (interface.go:120-126);
@@ -560,9 +563,10 @@ const int32_t* eppk_group_device_picks(eppk_group* g, uint32_t i);
  *                 request no round placed; EPPK_RANK_NONE for one without a valid entry
  * One pick per request: eppk_index_insert_picks_device takes d_out_pick as it is.  Asynchronous on `stream` (NULL = the context's);
  * always launches (also under EPPK_RESIDENT=1); ONE stream at a time per context for the bounded entry points (the scratch -- chunk
- * histograms, lists -- is per context and grows on demand: a call that has to grow it -- the first one, or a larger batch than ever before --
- * drains the DEVICE first, since queued work may still read the old buffers, so such a call is not asynchronous and cannot be captured
- * into a graph; run one batch of the largest size before capturing).  Requests are resolved in chunks of EPPK_BOUND_CHUNK rows (environment, read
+ * histograms, lists -- is per context and grows on demand: a call that has to REPLACE it -- a larger batch than ever before -- drains the
+ * DEVICE first, since queued work may still read the old buffers; the first call allocates it and drains nothing, no work can be reading
+ * a buffer that never existed.  Either call is not asynchronous and cannot be captured into a graph; run one batch of the largest size
+ * before capturing).  Requests are resolved in chunks of EPPK_BOUND_CHUNK rows (environment, read
  * at eppk_create: a power of two >= 64, default 512); a batch of at most one chunk takes a single launch, a larger one three per
  * round and one more.  Errors: EPPK_ERR_ARG for a null argument, k outside 1..EPPK_MAX_TOPK, an unknown policy, or while assumed load
  * is on (eppk_set_assumed_load: both count load; they do not combine); EPPK_ERR_NO_SNAPSHOT; the host-buffer forms EPPK_ERR_LIMIT for
@@ -606,8 +610,8 @@ int eppk_bounded_geometry(const eppk_ctx* ctx, uint32_t out[2]);
  *   bands         HOST memory, read at the call: n_bands (1 .. EPPK_MAX_BANDS) entries; reserve must not decrease from band to band
  *   every other argument as for the entry points above.
  * The same notes hold: asynchronous on `stream`; ONE stream at a time per context for the bounded and banded entry points; the scratch
- * (as above, and for a batch of more than one chunk a permutation, band histograms and segment bounds) grows on demand, and a call
- * that has to grow it drains the DEVICE first, is not asynchronous and cannot be captured into a graph.  A batch of at most one
+ * (as above, and for a batch of more than one chunk a permutation, band histograms and segment bounds) grows on demand: a call that
+ * replaces it drains the DEVICE first, a first call allocates it; neither is asynchronous or can be captured into a graph.  A batch of at most one
  * chunk takes a single launch; a larger one is put in band order first (three launches: a stable permutation, the lists are not
  * copied), then takes three launches per band and round -- the band's rows are found on the device, the *_device forms never wait
  * for the host -- and one more.  The host-buffer forms skip the launches of a band without requests.  Errors: as above, and
@@ -655,8 +659,8 @@ int eppk_group_pick_banded(eppk_group* g, const void* reqs, uint32_t n_reqs, con
  *   d_band NULL and a one-band table give the cost form of the plain bounded resolve.  Every other argument as above; the pick forms
  *   take per-request costs only (the caller cannot know the lists).
  * The same notes hold: asynchronous on `stream`; ONE stream at a time per context for the bounded, banded and costed entry points; the
- * scratch (as above, and the takers' totals per pod) grows on demand, and a call that has to grow it drains the DEVICE first, is not
- * asynchronous and cannot be captured into a graph.  A batch of at most one chunk takes a single launch; a larger one is put in band
+ * scratch (as above, and the takers' totals per pod) grows on demand: a call that replaces it drains the DEVICE first, a first call
+ * allocates it; neither is asynchronous or can be captured into a graph.  A batch of at most one chunk takes a single launch; a larger one is put in band
  * order first (three launches), then takes three launches per band and round -- the band's rows are found on the device, the *_device
  * forms never wait for the host -- and one more.  Always launches (also under EPPK_RESIDENT=1).  Errors: as above, and EPPK_ERR_ARG
  * for a null d_cost or an unknown bit in cost_flags. */
