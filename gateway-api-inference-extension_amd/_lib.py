@@ -18,6 +18,7 @@ EPPK_RANK_OVERFLOW, EPPK_RANK_NONE = 0x40, 0x80
 EPPK_MAX_BANDS = 8
 EPPK_MAX_COST = 0x00FFFFFF
 EPPK_COST_PER_ENTRY = 1
+EPPK_MAX_FLOWS = 1024
 
 STATUS = {0: "EPPK_OK", -1: "EPPK_ERR_ARG", -2: "EPPK_ERR_LIMIT", -3: "EPPK_ERR_DEVICE",
           -4: "EPPK_ERR_NO_SNAPSHOT", -5: "EPPK_ERR_INDEX_FULL", -6: "EPPK_ERR_NOMEM"}
@@ -39,6 +40,7 @@ SYMBOLS = [
     "eppk_bounded_resolve_device", "eppk_pick_bounded_device", "eppk_pick_bounded", "eppk_group_pick_bounded", "eppk_bounded_geometry",
     "eppk_banded_resolve_device", "eppk_pick_banded_device", "eppk_pick_banded", "eppk_group_pick_banded",
     "eppk_costed_resolve_device", "eppk_pick_costed_device", "eppk_pick_costed", "eppk_group_pick_costed",
+    "eppk_fair_resolve_device", "eppk_pick_fair_device", "eppk_pick_fair", "eppk_group_pick_fair",
     "eppk_group_create", "eppk_group_destroy", "eppk_group_last_error", "eppk_group_size", "eppk_group_ctx", "eppk_group_ranks_seen",
     "eppk_group_set_min_shard", "eppk_group_snapshot_publish", "eppk_group_index_clear", "eppk_group_index_insert",
     "eppk_group_index_remove_pod", "eppk_group_index_advance_epoch", "eppk_group_index_evict_older", "eppk_group_pick_batch",
@@ -172,6 +174,10 @@ def load_library() -> C.CDLL:
     lib.eppk_pick_costed_device.argtypes = [vp, vp, u32, vp, u32, vp, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp, vp]
     lib.eppk_pick_costed.argtypes = [vp, vp, u32, vp, u32, vp, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp]
     lib.eppk_group_pick_costed.argtypes = [vp, vp, u32, vp, u32, vp, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp]
+    lib.eppk_fair_resolve_device.argtypes = [vp, vp, vp, u32, u32, vp, u32, vp, u32, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp, vp]
+    lib.eppk_pick_fair_device.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp, vp]
+    lib.eppk_pick_fair.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp]
+    lib.eppk_group_pick_fair.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp]
     lib.eppk_group_create.argtypes = [C.POINTER(Cfg), C.POINTER(i32), u32, u32, C.POINTER(vp)]
     lib.eppk_group_destroy.argtypes = [vp]
     lib.eppk_group_destroy.restype = None

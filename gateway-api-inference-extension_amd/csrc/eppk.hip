@@ -12,6 +12,7 @@
 #include "eppk_bounded.hip.h"
 #include "eppk_banded.hip.h"
 #include "eppk_costed.hip.h"
+#include "eppk_fair.hip.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -225,6 +226,11 @@ struct eppk_ctx {
   // ... in cost units (SEMANTICS.md §3f; eppk_costed.hip.h)
   DBuf<uint32_t> d_cs_acc;                                  // [EPPK_MAX_PODS] takers' totals of a round, until the next scan pass folds them into the load
   DBuf<uint32_t> d_cs_cost;                                 // costs of the host forms (per request)
+  // ... with fair shares between flows (SEMANTICS.md §3g; eppk_fair.hip.h): perm, seg, d_bd_hist, d_cs_acc and the pod scratch are those above
+  DBuf<uint32_t> d_fr_fh;                                   // cnt[G] (rows per key, G = n_bands * n_flows), then [chunks][G] rows per key / those in front
+  DBuf<uint16_t> d_fr_key;                                  // a key per request (band * n_flows + flow, or 0xFFFF: not in the order)
+  DBuf<uint8_t> d_fr_band;                                  // the effective band byte per request: the band, or 0xFF for a row that is not in the order
+  DBuf<uint16_t> d_fr_flow;                                 // flow ids of the host forms
 
   // measurement
   bool prof = false;
@@ -3370,6 +3376,199 @@ int eppk_pick_costed(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint6
   return costed_host_finish(c, c->d_tk_pick, c->d_tk_score, n_reqs, k, cost, band, counts, tab, cap, cap_all, load, out_pick, out_score, out_rank);
 }
 
+// ---- ... with fair shares between flows (SEMANTICS.md §3g; eppk_fair.hip.h) ------------------------------------------------------
+
+namespace {
+
+// The arguments every fair entry point shares: those of the banded forms, n_flows, and a cost array that may be null (every cost 1).
+int fair_check(eppk_ctx* c, const char* who, uint32_t k, const eppk_band_table* t, uint32_t n_flows, const void* cost, uint32_t cost_flags,
+               eppk::BandTab* tab) {
+  const int rc = banded_check(c, who, k, t, tab);
+  if (rc) return rc;
+  if (n_flows < 1u || n_flows > EPPK_MAX_FLOWS)
+    return fail(c, EPPK_ERR_ARG, std::string(who) + ": n_flows out of range (1.." + std::to_string(EPPK_MAX_FLOWS) + ")");
+  if (cost_flags & ~EPPK_COST_PER_ENTRY) return fail(c, EPPK_ERR_ARG, std::string(who) + ": unknown cost flags " + std::to_string(cost_flags));
+  if (!cost && cost_flags) return fail(c, EPPK_ERR_ARG, std::string(who) + ": cost flags " + std::to_string(cost_flags) + " with a null cost (every cost is 1)");
+  return EPPK_OK;
+}
+
+// Band bytes, flow ids and costs of a host form, before anything is launched: the lowest bad row is named; the rows per band are counted.
+int fair_host_counts(eppk_ctx* c, const char* who, const uint8_t* band, const uint16_t* flow, uint32_t n_flows, const uint32_t* cost, uint32_t n_reqs,
+                     uint32_t n_bands, uint32_t counts[EPPK_MAX_BANDS]) {
+  for (uint32_t b = 0; b < EPPK_MAX_BANDS; ++b) counts[b] = 0u;
+  for (uint32_t r = 0; r < n_reqs; ++r) {
+    const uint32_t b = band ? band[r] : 0u, f = flow ? flow[r] : 0u;
+    if (b >= n_bands)
+      return fail(c, EPPK_ERR_ARG, std::string(who) + ": request row " + std::to_string(r) + " names band " + std::to_string(b) + " of " + std::to_string(n_bands));
+    if (f >= n_flows)
+      return fail(c, EPPK_ERR_ARG, std::string(who) + ": request row " + std::to_string(r) + " names flow " + std::to_string(f) + " of " + std::to_string(n_flows));
+    if (cost && cost[r] - 1u >= EPPK_MAX_COST)
+      return fail(c, EPPK_ERR_ARG, std::string(who) + ": request row " + std::to_string(r) + " has cost " + std::to_string(cost[r]) + " (1.." +
+                                       std::to_string(EPPK_MAX_COST) + ")");
+    ++counts[b];
+  }
+  return EPPK_OK;
+}
+
+// The launches of the fair resolve on `st` (arguments checked by the caller; n_reqs != 0).  Always the permutation route: the fair order
+// (fair_hist_kernel, fair_offsets_kernel, fair_scatter_kernel) where banded_resolve / costed_resolve put the band order, then their
+// round kernels per band -- the costed ones, or with a null d_cost the banded ones -- and their finish, all reading the effective band
+// bytes.  `counts` as for banded_resolve.
+int fair_resolve(eppk_ctx* c, const int32_t* d_lists, const double* d_scores, uint32_t n_reqs, uint32_t k, const uint16_t* d_flow, uint32_t n_flows,
+                 const uint32_t* d_cost, uint32_t cost_flags, const uint8_t* d_band, const eppk::BandTab& tab, const uint32_t* counts, const uint32_t* d_cap,
+                 uint32_t cap_all, uint32_t* d_load, int32_t* d_out_pick, double* d_out_score, uint8_t* d_out_rank, hipStream_t st) {
+  const uint32_t P = c->n_pods, chunk = c->bound_chunk;
+  const eppk::CostOf cost{d_cost, k, cost_flags & EPPK_COST_PER_ENTRY};
+  const size_t G = (size_t)tab.n_bands * n_flows;
+  int rc;
+  uint8_t* state = d_out_rank;
+  if (!state) {
+    if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_bd_state, 1u, "bounded picker: request states"}}))) return rc;
+    state = c->d_bd_state;
+  }
+  const uint32_t n_chunks = (uint32_t)(((uint64_t)n_reqs + chunk - 1u) / chunk);
+  if ((rc = bounded_pod_scratch(c))) return rc;
+  if ((rc = ctx_grow(c, (size_t)n_chunks * P, {{c->d_bd_hist, sizeof(uint32_t), "bounded picker: bid histogram"}}))) return rc;
+  if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_bn_perm, sizeof(uint32_t), "banded picker: band order"}}))) return rc;
+  if ((rc = ctx_grow(c, eppk::kBandSegWords + (size_t)n_chunks * EPPK_MAX_BANDS, {{c->d_bn_bh, sizeof(uint32_t), "banded picker: band histogram"}}))) return rc;
+  if ((rc = ctx_grow(c, (size_t)EPPK_MAX_PODS, {{c->d_cs_acc, sizeof(uint32_t), "costed picker: takers' totals"}}))) return rc;
+  if ((rc = ctx_grow(c, G + (size_t)n_chunks * G, {{c->d_fr_fh, sizeof(uint32_t), "fair picker: flow histogram"}}))) return rc;
+  if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_fr_key, sizeof(uint16_t), "fair picker: keys"}, {c->d_fr_band, 1u, "fair picker: effective bands"}}))) return rc;
+  uint32_t* seg = c->d_bn_bh;
+  uint32_t* cnt = c->d_fr_fh;
+  uint32_t* fh = c->d_fr_fh + G;
+  uint32_t* perm = c->d_bn_perm;
+  uint32_t* room = c->d_bd_pods;
+  uint32_t* acc = c->d_cs_acc;
+  const uint8_t* eband = c->d_fr_band;
+  uint32_t* load = d_load;
+  if (!load) {
+    load = c->d_bd_pods + EPPK_MAX_PODS;
+    HIPCHK(c, hipMemsetAsync(load, 0, (size_t)EPPK_MAX_PODS * sizeof(uint32_t), st));
+  }
+  if (d_cost) HIPCHK(c, hipMemsetAsync(acc, 0, (size_t)EPPK_MAX_PODS * sizeof(uint32_t), st));
+  HIPCHK(c, hipMemsetAsync(seg, 0, (size_t)eppk::kBandSegWords * sizeof(uint32_t), st));
+  HIPCHK(c, hipMemsetAsync(state, (int)eppk::kBoundUnassigned, n_reqs, st));
+  // grid-stride loops as wide as the CUs this context may use (EPPK_MAX_CU): the results do not depend on the width
+  const uint32_t wide = (uint32_t)c->num_cu * 4u;
+  const uint32_t chunk_grid = n_chunks < wide ? n_chunks : wide;
+  const uint32_t pod_wgs = (P + eppk::kBoundScanPods - 1u) / eppk::kBoundScanPods, pod_grid = pod_wgs < wide ? pod_wgs : wide;
+  const uint32_t key_wgs = (uint32_t)((G + eppk::kBoundScanPods - 1u) / eppk::kBoundScanPods), key_grid = key_wgs < wide ? key_wgs : wide;
+  const uint32_t row_wgs = (uint32_t)(((uint64_t)n_reqs + eppk::kBoundThreads - 1u) / eppk::kBoundThreads), row_grid = row_wgs < wide * 2u ? row_wgs : wide * 2u;
+  hipLaunchKernelGGL(eppk::fair_hist_kernel, dim3(chunk_grid), dim3(eppk::kBoundThreads), 0, st, d_band, d_flow, n_reqs, tab.n_bands, n_flows, chunk, n_chunks, fh,
+                     (uint16_t*)c->d_fr_key, (uint8_t*)c->d_fr_band);
+  hipLaunchKernelGGL(eppk::fair_offsets_kernel, dim3(key_grid), dim3(eppk::kBoundScanSegs * eppk::kBoundScanPods), 0, st, fh, n_chunks, tab.n_bands, n_flows, cnt, seg);
+  hipLaunchKernelGGL(eppk::fair_scatter_kernel, dim3(chunk_grid), dim3(64), 2u * G * sizeof(uint32_t), st, (const uint16_t*)c->d_fr_key, n_reqs, tab.n_bands, n_flows, chunk, n_chunks,
+                     (const uint32_t*)fh, (const uint32_t*)cnt, (const uint32_t*)seg, perm);
+  if (P) for (uint32_t b = 0; b < tab.n_bands; ++b) {
+    uint32_t band_grid = chunk_grid;
+    if (counts) {
+      if (!counts[b]) continue;
+      const uint32_t band_chunks = (uint32_t)(((uint64_t)counts[b] + chunk - 1u) / chunk);
+      band_grid = band_chunks < wide ? band_chunks : wide;
+    }
+    const eppk::CostRoomGlobal room_now{d_cap, cap_all, tab.reserve[b], load, acc};
+    for (uint32_t j = 0; j < k; ++j) {
+      if (d_cost) {
+        hipLaunchKernelGGL(eppk::costed_count_kernel, dim3(band_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, k, j, P, chunk, (const uint32_t*)seg, b,
+                           (const uint32_t*)perm, cost, room_now, state, c->d_bd_hist);
+        hipLaunchKernelGGL(eppk::costed_scan_kernel, dim3(pod_grid), dim3(eppk::kBoundScanSegs * eppk::kBoundScanPods), 0, st, c->d_bd_hist, chunk,
+                           (const uint32_t*)seg, b, P, d_cap, cap_all, tab.reserve[b], load, acc, room);
+        hipLaunchKernelGGL(eppk::costed_assign_kernel, dim3(band_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, d_scores, k, j, P, chunk, (const uint32_t*)seg,
+                           b, (const uint32_t*)perm, cost, (const uint32_t*)c->d_bd_hist, (const uint32_t*)room, acc, state, d_out_pick, d_out_score);
+      } else {
+        hipLaunchKernelGGL(eppk::banded_count_kernel, dim3(band_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, k, j, P, chunk, (const uint32_t*)seg, b,
+                           (const uint32_t*)perm, (const uint8_t*)state, c->d_bd_hist);
+        hipLaunchKernelGGL(eppk::banded_scan_kernel, dim3(pod_grid), dim3(eppk::kBoundScanSegs * eppk::kBoundScanPods), 0, st, c->d_bd_hist, chunk,
+                           (const uint32_t*)seg, b, P, d_cap, cap_all, tab.reserve[b], load, room);
+        hipLaunchKernelGGL(eppk::banded_assign_kernel, dim3(band_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, d_scores, k, j, P, chunk, (const uint32_t*)seg,
+                           b, (const uint32_t*)perm, (const uint32_t*)c->d_bd_hist, (const uint32_t*)room, state, d_out_pick, d_out_score);
+      }
+    }
+  }
+  if (d_cost)
+    hipLaunchKernelGGL(eppk::costed_finish_kernel, dim3(row_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, d_scores, n_reqs, k, P, cost, eband, tab.n_bands,
+                       tab.spill, load, (const uint32_t*)acc, state, d_out_pick, d_out_score, c->d_status);
+  else
+    hipLaunchKernelGGL(eppk::banded_finish_kernel, dim3(row_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, d_scores, n_reqs, k, P, eband, tab.n_bands, tab.spill,
+                       load, state, d_out_pick, d_out_score, c->d_status);
+  HIPCHK(c, hipGetLastError());
+  return EPPK_OK;
+}
+
+// Band bytes, flow ids and costs up (checked and counted by fair_host_counts), then as bounded_host_finish.
+int fair_host_finish(eppk_ctx* c, const int32_t* d_lists, const double* d_scores, uint32_t n_reqs, uint32_t k, const uint16_t* flow, uint32_t n_flows,
+                     const uint32_t* cost, const uint8_t* band, const uint32_t* counts, const eppk::BandTab& tab, const uint32_t* cap, uint32_t cap_all,
+                     uint32_t* load, int32_t* out_pick, double* out_score, uint8_t* out_rank) {
+  int rc;
+  if (band) {
+    if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_bn_band, 1u, "banded picker: bands"}}))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_bn_band, band, n_reqs, hipMemcpyHostToDevice, c->stream));
+  }
+  if (flow) {
+    if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_fr_flow, sizeof(uint16_t), "fair picker: flows"}}))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_fr_flow, flow, (size_t)n_reqs * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+  }
+  if (cost) {
+    if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_cs_cost, sizeof(uint32_t), "costed picker: costs"}}))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_cs_cost, cost, (size_t)n_reqs * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  }
+  return bounded_host_around(c, n_reqs, cap, load, out_pick, out_score, out_rank,
+                             [&](const uint32_t* d_cap, uint32_t* d_load, int32_t* d_pick, double* d_score, uint8_t* d_rank) {
+                               return fair_resolve(c, d_lists, d_scores, n_reqs, k, flow ? (const uint16_t*)c->d_fr_flow : nullptr, n_flows,
+                                                   cost ? (const uint32_t*)c->d_cs_cost : nullptr, 0u, band ? (const uint8_t*)c->d_bn_band : nullptr, tab, counts,
+                                                   d_cap, cap_all, d_load, d_pick, d_score, d_rank, c->stream);
+                             });
+}
+
+}  // namespace
+
+int eppk_fair_resolve_device(eppk_ctx* c, const int32_t* d_lists, const double* d_list_scores, uint32_t n_reqs, uint32_t k, const uint16_t* d_flow,
+                             uint32_t n_flows, const uint32_t* d_cost, uint32_t cost_flags, const uint8_t* d_band, const eppk_band_table* bands,
+                             const uint32_t* d_cap, uint32_t cap_all, uint32_t* d_load, int32_t* d_out_pick, double* d_out_score, uint8_t* d_out_rank,
+                             void* stream) {
+  if (!c || ((!d_lists || !d_out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_fair_resolve_device: null argument");
+  eppk::BandTab tab;
+  const int rcc = fair_check(c, "eppk_fair_resolve_device", k, bands, n_flows, d_cost, cost_flags, &tab);
+  if (rcc) return rcc;
+  if (n_reqs == 0) return EPPK_OK;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  return fair_resolve(c, d_lists, d_list_scores, n_reqs, k, d_flow, n_flows, d_cost, cost_flags, d_band, tab, nullptr, d_cap, cap_all, d_load, d_out_pick,
+                      d_out_score, d_out_rank, stream ? (hipStream_t)stream : c->stream);
+}
+
+int eppk_pick_fair_device(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, uint32_t k, const uint16_t* d_flow, uint32_t n_flows,
+                          const uint32_t* d_cost, const uint8_t* d_band, const eppk_band_table* bands, const uint32_t* d_cap, uint32_t cap_all,
+                          uint32_t* d_load, int32_t* d_out_pick, double* d_out_score, uint8_t* d_out_rank, void* stream) {
+  if (!c || ((!d_reqs || !d_out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_fair_device: null argument");
+  eppk::BandTab tab;
+  int rc = fair_check(c, "eppk_pick_fair_device", k, bands, n_flows, d_cost, 0u, &tab);
+  if (rc) return rc;
+  if (n_reqs == 0) return EPPK_OK;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if ((rc = bounded_lists(c, n_reqs))) return rc;
+  if ((rc = eppk_pick_topk_device(c, d_reqs, n_reqs, d_cand_mask, k, c->d_bd_list, c->d_bd_lscore, stream))) return rc;
+  return fair_resolve(c, c->d_bd_list, c->d_bd_lscore, n_reqs, k, d_flow, n_flows, d_cost, 0u, d_band, tab, nullptr, d_cap, cap_all, d_load, d_out_pick,
+                      d_out_score, d_out_rank, stream ? (hipStream_t)stream : c->stream);
+}
+
+int eppk_pick_fair(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint16_t* flow, uint32_t n_flows,
+                   const uint32_t* cost, const uint8_t* band, const eppk_band_table* bands, const uint32_t* cap, uint32_t cap_all, uint32_t* load,
+                   int32_t* out_pick, double* out_score, uint8_t* out_rank) {
+  if (!c || ((!reqs || !out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_fair: null argument");
+  eppk::BandTab tab;
+  int rc = fair_check(c, "eppk_pick_fair", k, bands, n_flows, cost, 0u, &tab);
+  if (rc) return rc;
+  if (n_reqs > c->cfg.max_batch) return fail(c, EPPK_ERR_LIMIT, "eppk_pick_fair: n_reqs > max_batch");
+  if (n_reqs == 0) return EPPK_OK;
+  if ((rc = validate_rows(c, "eppk_pick_fair", reqs, n_reqs))) return rc;
+  uint32_t counts[EPPK_MAX_BANDS];
+  if ((rc = fair_host_counts(c, "eppk_pick_fair", band, flow, n_flows, cost, n_reqs, tab.n_bands, counts))) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if ((rc = bounded_host_lists(c, reqs, n_reqs, cand_mask, k))) return rc;
+  return fair_host_finish(c, c->d_tk_pick, c->d_tk_score, n_reqs, k, flow, n_flows, cost, band, counts, tab, cap, cap_all, load, out_pick, out_score, out_rank);
+}
+
 // ---- on-device prompt hashing ------------------------------------------------------------------------
 
 int eppk_hash_prompts_device(eppk_ctx* c, const void* d_prompts, uint64_t prompt_stride, const uint32_t* d_prompt_len,
@@ -4050,6 +4249,33 @@ int eppk_group_pick_costed(eppk_group* g, const void* reqs, uint32_t n_reqs, con
       hipMemcpyAsync(c0->d_bd_lscore, totals.data(), totals.size() * 8u, hipMemcpyHostToDevice, c0->stream) != hipSuccess)
     return gfail(g, EPPK_ERR_DEVICE, "eppk_group_pick_costed: upload failed");
   if ((rc = costed_host_finish(c0, c0->d_bd_list, c0->d_bd_lscore, n_reqs, k, cost, band, counts, tab, cap, cap_all, load, out_pick, out_score, out_rank)))
+    return mfail(rc);
+  return EPPK_OK;
+}
+
+int eppk_group_pick_fair(eppk_group* g, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint16_t* flow, uint32_t n_flows,
+                         const uint32_t* cost, const uint8_t* band, const eppk_band_table* bands, const uint32_t* cap, uint32_t cap_all, uint32_t* load,
+                         int32_t* out_pick, double* out_score, uint8_t* out_rank) {
+  if (!g || ((!reqs || !out_pick) && n_reqs)) return gfail(g, EPPK_ERR_ARG, "eppk_group_pick_fair: null argument");
+  eppk_ctx* c0 = g->ctx[0];
+  eppk::BandTab tab;
+  uint32_t counts[EPPK_MAX_BANDS];
+  int rc = fair_check(c0, "eppk_group_pick_fair", k, bands, n_flows, cost, 0u, &tab);
+  if (!rc) rc = fair_host_counts(c0, "eppk_group_pick_fair", band, flow, n_flows, cost, n_reqs, tab.n_bands, counts);
+  if (rc) return gfail(g, rc, eppk_last_error(c0));
+  // as eppk_group_pick_bounded: the lists of the whole batch on the host, then ONE resolve on member 0
+  std::vector<int32_t> lists((size_t)n_reqs * k);
+  std::vector<double> totals((size_t)n_reqs * k);
+  if ((rc = group_topk(g, "eppk_group_pick_fair", reqs, n_reqs, cand_mask, k, false, 0ull, lists.data(), totals.data()))) return rc;
+  if (n_reqs == 0) return EPPK_OK;
+  auto mfail = [&](int code) { return gfail(g, code, "device " + std::to_string(g->dev[0]) + ": " + eppk_last_error(c0)); };
+  if (hipSetDevice(g->dev[0]) != hipSuccess) return gfail(g, EPPK_ERR_DEVICE, "eppk_group_pick_fair: hipSetDevice failed");
+  if ((rc = bounded_lists(c0, n_reqs))) return mfail(rc);
+  if (hipMemcpyAsync(c0->d_bd_list, lists.data(), lists.size() * 4u, hipMemcpyHostToDevice, c0->stream) != hipSuccess ||
+      hipMemcpyAsync(c0->d_bd_lscore, totals.data(), totals.size() * 8u, hipMemcpyHostToDevice, c0->stream) != hipSuccess)
+    return gfail(g, EPPK_ERR_DEVICE, "eppk_group_pick_fair: upload failed");
+  if ((rc = fair_host_finish(c0, c0->d_bd_list, c0->d_bd_lscore, n_reqs, k, flow, n_flows, cost, band, counts, tab, cap, cap_all, load, out_pick, out_score,
+                             out_rank)))
     return mfail(rc);
   return EPPK_OK;
 }

@@ -719,6 +719,8 @@ struct Request {  // interface.go:35-44
   uint8_t band = 0;                              // priority band, 0 = the most important (SEMANTICS.md §3e); read by a Bounded profile with bands
   uint32_t cost = 1;                             // what the request takes of an endpoint's cap, 1 .. EPPK_MAX_COST (SEMANTICS.md §3f: prompt blocks);
                                                  // read by a costed Bounded profile
+  uint16_t flow = 0;                             // the request's flow, below ProfileSpec::n_flows (SEMANTICS.md §3g: the bucket of its fairness id);
+                                                 // read by a Bounded profile with n_flows
 };
 
 struct ScoredEndpoint {  // interface.go:50-53
@@ -752,6 +754,9 @@ struct ProfileSpec {
                                                  // bounded_policy is not read.  Empty = no bands: batch order alone decides (§3d)
   bool costed = false;                           // bounded: cap_all and the reserves are in COST units and every request takes Request::cost of
                                                  // them (SEMANTICS.md §3f; eppk_pick_costed).  Empty `bands` = one band with bounded_policy
+  uint32_t n_flows = 0;                          // bounded: > 0 (at most EPPK_MAX_FLOWS): inside a band the flows take turns, round-robin over
+                                                 // Request::flow in flow-id order, where batch order alone decided (SEMANTICS.md §3g;
+                                                 // eppk_pick_fair); with or without `bands` and `costed`.  0 = off
   std::vector<eppk_predicate> predicates;        // metric predicates behind `filter` (SEMANTICS.md §2c): ONE program, evaluated on the device
                                                  // against the gauges of the snapshot; empty = none.  A request they shed gets Unavailable.
 };
@@ -804,6 +809,8 @@ class Scheduler {  // interface.go:55-66
       // (a cap of 0 leaves no room on any endpoint: every request would end as Unavailable -- a profile that forgot to set it)
       if (ps.picker == PickerKind::Bounded && ps.cap_all == 0) return {Code::Internal, std::string("profile ") + ps.name + ": the bounded picker needs cap_all > 0"};
       if (ps.costed && ps.picker != PickerKind::Bounded) return {Code::Internal, std::string("profile ") + ps.name + ": costed needs the bounded picker"};
+      if (ps.n_flows && ps.picker != PickerKind::Bounded) return {Code::Internal, std::string("profile ") + ps.name + ": n_flows needs the bounded picker"};
+      if (ps.n_flows > EPPK_MAX_FLOWS) return {Code::Internal, std::string("profile ") + ps.name + ": more than " + std::to_string(EPPK_MAX_FLOWS) + " flows"};
       if (ps.bands.size() > EPPK_MAX_BANDS) return {Code::Internal, std::string("profile ") + ps.name + ": more than 8 bands"};
       for (size_t b = 1; b < ps.bands.size(); ++b)
         if (ps.bands[b].reserve < ps.bands[b - 1].reserve)
@@ -852,7 +859,7 @@ class Scheduler {  // interface.go:55-66
     const size_t n = requests.size();
     std::vector<std::map<std::string, std::vector<ScoredEndpoint>>> results(n);
     const size_t stride = 8u + 8u * opt_.max_blocks;
-    std::vector<std::string> refused(n);              // a request a costed profile cannot take: its own Internal status, the batch goes on
+    std::vector<std::string> refused(n);              // a request a costed or fair profile cannot take: its own Internal status, the batch goes on
     for (int round = 0; round < 16; ++round) {        // (a handler that never stops is cut off)
       std::map<std::string, std::vector<uint32_t>> group;
       for (size_t r = 0; r < n; ++r)
@@ -861,6 +868,11 @@ class Scheduler {  // interface.go:55-66
           if (requests[r].cost - 1u >= EPPK_MAX_COST && Costed(name)) {   // before the call: the library would refuse the whole batch
             results[r][name];                                             // (the profile has run, without an endpoint)
             refused[r] = "profile " + name + ": request cost " + std::to_string(requests[r].cost) + " out of range (1.." + std::to_string(EPPK_MAX_COST) + ")";
+            continue;
+          }
+          if (const uint32_t nf = Flows(name); nf && requests[r].flow >= nf) {   // as a bad cost: the request's own status, the batch goes on
+            results[r][name];
+            refused[r] = "profile " + name + ": request flow " + std::to_string(requests[r].flow) + " out of range (0.." + std::to_string(nf - 1u) + ")";
             continue;
           }
           group[name].push_back((uint32_t)r);
@@ -909,15 +921,20 @@ class Scheduler {  // interface.go:55-66
           }
           const bool costed = p.spec.picker == PickerKind::Bounded && p.spec.costed;
           const bool banded = p.spec.picker == PickerKind::Bounded && !p.spec.bands.empty();
+          const bool fair = p.spec.picker == PickerKind::Bounded && p.spec.n_flows != 0u;
           eppk_band_table table;
+          if (fair) {
+            flows_.resize(m);
+            for (uint32_t i = 0; i < m; ++i) flows_[i] = requests[idx[lo + i]].flow;
+          }
           if (costed) {
             costs_.resize(m);
             for (uint32_t i = 0; i < m; ++i) costs_[i] = requests[idx[lo + i]].cost;
-            if (!banded) {                                             // one band with the profile's policy: the cost form of §3d
-              std::memset(&table, 0, sizeof table);
-              table.n_bands = 1u;
-              table.policy[0] = p.spec.bounded_policy;
-            }
+          }
+          if ((costed || fair) && !banded) {                           // one band with the profile's policy: the cost / fair form of §3d
+            std::memset(&table, 0, sizeof table);
+            table.n_bands = 1u;
+            table.policy[0] = p.spec.bounded_policy;
           }
           if (banded) {
             std::memset(&table, 0, sizeof table);
@@ -931,6 +948,10 @@ class Scheduler {  // interface.go:55-66
                              ? eppk_pick_filtered(p.ctx.get(), rows, m, nullptr, nullptr, 1, picks_.data(), scores_.data(), nullptr)
                          : p.spec.picker == PickerKind::BestScore
                              ? eppk_pick_batch(p.ctx.get(), rows, m, nullptr, picks_.data(), scores_.data())
+                         : fair
+                             ? eppk_pick_fair(p.ctx.get(), rows, m, fmask, p.spec.k, flows_.data(), p.spec.n_flows, costed ? costs_.data() : nullptr,
+                                              banded ? bands_.data() : nullptr, &table, nullptr, p.spec.cap_all, nullptr, picks_.data(), scores_.data(),
+                                              nullptr)
                          : costed
                              ? eppk_pick_costed(p.ctx.get(), rows, m, fmask, p.spec.k, costs_.data(), banded ? bands_.data() : nullptr, &table, nullptr,
                                                 p.spec.cap_all, nullptr, picks_.data(), scores_.data(), nullptr)
@@ -972,6 +993,10 @@ class Scheduler {  // interface.go:55-66
     for (const Prof& p : profiles_) if (p.spec.name == profile) return p.spec.costed;
     return false;
   }
+  uint32_t Flows(const std::string& profile) const {
+    for (const Prof& p : profiles_) if (p.spec.name == profile) return p.spec.picker == PickerKind::Bounded ? p.spec.n_flows : 0u;
+    return 0u;
+  }
   Options opt_;
   ProfileHandler* handler_ = nullptr;
   std::vector<Prof> profiles_;
@@ -984,6 +1009,7 @@ class Scheduler {  // interface.go:55-66
   std::vector<uint64_t> fmask_;
   std::vector<uint8_t> bands_;
   std::vector<uint32_t> costs_;
+  std::vector<uint16_t> flows_;
 };
 
 }  // namespace eppk_host

@@ -245,6 +245,18 @@ def _cost_words(cost, n_reqs: int):
     return np.ascontiguousarray(a, dtype=np.uint32)
 
 
+def _flow_words(flow, n_reqs: int):
+    """The flow id per request as a u16 array, or None (every request in flow 0); an id that does not fit 16 bits is refused here, the
+    library checks it against n_flows."""
+    if flow is None:
+        return None
+    a = np.asarray(flow)
+    assert a.shape == (n_reqs,), "one flow id per request"
+    if a.size and (a.min() < 0 or a.max() > 0xFFFF):
+        raise EppkError(-1, "fair pick: flow id out of range (u16)")
+    return np.ascontiguousarray(a, dtype=np.uint16)
+
+
 class RoundRobinPicker:
     """server.go:84-101 — the reference's picker; the shim's fail-open fallback."""
 
@@ -722,6 +734,52 @@ class BatchedPicker:
                                                          d_band or None, C.byref(_band_table(bands)), d_cap or None, int(cap_all), d_load or None,
                                                          d_pick, d_score or None, d_rank or None, stream or None), "bounded_resolve_costed_device")
 
+    # -- ... with fair shares between flows (SEMANTICS.md §3g) ----------------------------------------
+    def pick_bounded_fair(self, reqs: np.ndarray, k: int, flow, n_flows: int, cost, cap, bands=((_lib.EPPK_BOUNDED_SHED, 0),),
+                          band: Optional[np.ndarray] = None, load: Optional[np.ndarray] = None, mask: Optional[np.ndarray] = None
+                          ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray]]:
+        """eppk_pick_fair: pick_bounded_costed with a flow id per request (u16 [R] below n_flows, None: all in flow 0); inside a band
+        the flows take turns, round-robin in flow-id order.  `cost` None: every cost is 1.  Returns what pick_bounded returns."""
+        reqs = np.ascontiguousarray(reqs, dtype=np.uint64)
+        assert reqs.ndim == 2 and reqs.shape[1] == self.row_words, "request row stride mismatch"
+        R = reqs.shape[0]
+        mptr = None
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint64)
+            assert mask.shape == (R, (self.n_pods + 63) // 64), "mask shape mismatch"
+            mptr = mask.ctypes.data
+        cap_arr, cap_all, load = _bounded_caps(self.n_pods, cap, load)
+        band = _band_bytes(band, R)
+        flow = _flow_words(flow, R)
+        cost = None if cost is None else _cost_words(cost, R)
+        picks = np.full(R, -1, dtype=np.int32)
+        scores = np.zeros(R, dtype=np.float64)
+        ranks = np.full(R, _lib.EPPK_RANK_NONE, dtype=np.uint8)
+        self._check(self._lib.eppk_pick_fair(self._ctx, reqs.ctypes.data, R, mptr, int(k), flow.ctypes.data if flow is not None else None,
+                                             int(n_flows), cost.ctypes.data if cost is not None else None,
+                                             band.ctypes.data if band is not None else None, C.byref(_band_table(bands)),
+                                             cap_arr.ctypes.data if cap_arr is not None else None, cap_all,
+                                             load.ctypes.data if load is not None else None, picks.ctypes.data, scores.ctypes.data,
+                                             ranks.ctypes.data), "pick_bounded_fair")
+        return picks, scores, ranks, load
+
+    def pick_bounded_fair_device(self, d_reqs: int, n_reqs: int, d_mask: Optional[int], k: int, d_flow: Optional[int], n_flows: int,
+                                 d_cost: Optional[int], d_band: Optional[int], bands, d_cap: Optional[int], cap_all: int, d_load: Optional[int],
+                                 d_pick: int, d_score: Optional[int], d_rank: Optional[int], stream: int = 0) -> None:
+        """eppk_pick_fair_device: device pointers as ints (d_flow: n_reqs u16 or None; d_cost: n_reqs u32 or None), asynchronous on `stream`."""
+        self._check(self._lib.eppk_pick_fair_device(self._ctx, d_reqs, n_reqs, d_mask or None, int(k), d_flow or None, int(n_flows), d_cost or None,
+                                                    d_band or None, C.byref(_band_table(bands)), d_cap or None, int(cap_all), d_load or None, d_pick,
+                                                    d_score or None, d_rank or None, stream or None), "pick_bounded_fair_device")
+
+    def bounded_resolve_fair_device(self, d_lists: int, d_list_scores: Optional[int], n_reqs: int, k: int, d_flow: Optional[int], n_flows: int,
+                                    d_cost: Optional[int], cost_flags: int, d_band: Optional[int], bands, d_cap: Optional[int], cap_all: int,
+                                    d_load: Optional[int], d_pick: int, d_score: Optional[int], d_rank: Optional[int], stream: int = 0) -> None:
+        """eppk_fair_resolve_device: the fair resolve alone, over any [n_reqs][k] lists on the device."""
+        self._check(self._lib.eppk_fair_resolve_device(self._ctx, d_lists, d_list_scores or None, n_reqs, int(k), d_flow or None, int(n_flows),
+                                                       d_cost or None, int(cost_flags), d_band or None, C.byref(_band_table(bands)), d_cap or None,
+                                                       int(cap_all), d_load or None, d_pick, d_score or None, d_rank or None, stream or None),
+                    "bounded_resolve_fair_device")
+
     def bounded_geometry(self) -> Tuple[int, int]:
         """(rows per chunk, the largest batch the one-launch kernel takes) of the bounded resolve (EPPK_BOUND_CHUNK)."""
         out = (C.c_uint32 * 2)()
@@ -1039,6 +1097,27 @@ class DeviceGroup:
                                                      cap_arr.ctypes.data if cap_arr is not None else None, cap_all,
                                                      load.ctypes.data if load is not None else None, picks.ctypes.data, scores.ctypes.data,
                                                      ranks.ctypes.data), "group_pick_bounded_costed")
+        return picks, scores, ranks, load
+
+    def pick_bounded_fair(self, reqs: np.ndarray, k: int, flow, n_flows: int, cost, cap, bands=((_lib.EPPK_BOUNDED_SHED, 0),),
+                          band: Optional[np.ndarray] = None, load: Optional[np.ndarray] = None, mask: Optional[np.ndarray] = None
+                          ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray]]:
+        """eppk_group_pick_fair: BatchedPicker.pick_bounded_fair over the group."""
+        reqs, mask, mptr = self._rows_and_mask(reqs, mask)
+        R = reqs.shape[0]
+        cap_arr, cap_all, load = _bounded_caps(self.n_pods, cap, load)
+        band = _band_bytes(band, R)
+        flow = _flow_words(flow, R)
+        cost = None if cost is None else _cost_words(cost, R)
+        picks = np.full(R, -1, dtype=np.int32)
+        scores = np.zeros(R, dtype=np.float64)
+        ranks = np.full(R, _lib.EPPK_RANK_NONE, dtype=np.uint8)
+        self._check(self._lib.eppk_group_pick_fair(self._g, reqs.ctypes.data, R, mptr, int(k), flow.ctypes.data if flow is not None else None,
+                                                   int(n_flows), cost.ctypes.data if cost is not None else None,
+                                                   band.ctypes.data if band is not None else None, C.byref(_band_table(bands)),
+                                                   cap_arr.ctypes.data if cap_arr is not None else None, cap_all,
+                                                   load.ctypes.data if load is not None else None, picks.ctypes.data, scores.ctypes.data,
+                                                   ranks.ctypes.data), "group_pick_bounded_fair")
         return picks, scores, ranks, load
 
     # -- the pipelined host path over the group (eppk_group_pick_stage_*) ---------------------------------------------

@@ -682,6 +682,55 @@ int eppk_group_pick_costed(eppk_group* g, const void* reqs, uint32_t n_reqs, con
                            const uint8_t* band, const eppk_band_table* bands, const uint32_t* cap, uint32_t cap_all, uint32_t* load,
                            int32_t* out_pick, double* out_score, uint8_t* out_rank);
 
+/* ---- ... with fair shares between flows (SEMANTICS.md §3g) ---------------------------------------------------------------------
+ * The entry points above decide who gets a pod's room by band first and inside a band by BATCH ORDER alone: one tenant whose requests
+ * sit at the front of a batch takes every slot of its band.  The reference names fairness between flows inside a priority band as
+ * the flow controller's job (docs/proposals/0683-epp-architecture-proposal) and carries a fairness id per request (the header
+ * x-gateway-inference-fairness-id, docs/proposals/1199-inferencemodel-api-evolution).  Here every request carries a FLOW id below
+ * n_flows (a shim hashes fairness ids into n_flows buckets).  A row is IN THE ORDER iff band < n_bands and flow < n_flows; its TURN q is
+ * the number of rows in front of it in the batch that are in the order with the same band and the same flow (the same flow id in two
+ * bands is two flows).  The FAIR ORDER of band b is its rows sorted by (q, flow) ascending: the first request of every flow in flow-id
+ * order, then the second of every flow that has one, and so on.  Band b's rows then go through the costed resolve above with the fair
+ * order in place of batch order -- with d_cost NULL through the banded resolve -- and nothing else changes: the rounds, the bidder rule,
+ * "the first min(room, ...) of a pod's bidders", the prefix sums of cost, the single finish behind the last band, the rank bytes,
+ * EPPK_LAUNCH_BAD_PICK.  The result is a pure function of the arguments.  n_flows = 1 or d_flow NULL is eppk_costed_resolve_device bit
+ * for bit (d_cost NULL: eppk_banded_resolve_device); d_cost NULL equals a cost array of ones.
+ *   d_flow        nullable [n_reqs] u16; NULL: every request is in flow 0.  A flow >= n_flows behaves exactly like a band byte
+ *                 >= n_bands: on the *_device forms the row takes no room, gets EPPK_NO_PICK / 0.0 / EPPK_RANK_NONE and raises
+ *                 EPPK_LAUNCH_BAD_REQUEST_ROW (its list is still checked); the host-buffer forms refuse the batch with EPPK_ERR_ARG
+ *                 and name the lowest bad row.
+ *   n_flows       1 .. EPPK_MAX_FLOWS
+ *   d_cost        nullable here: NULL means every cost is 1 (the count units of the banded entry points), and cost_flags must be 0.
+ *                 A row whose cost is bad is in the order all the same -- the order looks only at band and flow -- holds its turn and
+ *                 bids for nothing.
+ *   every other argument as for the costed entry points; the pick forms take per-request costs or NULL.
+ * The same notes hold: asynchronous on `stream`; ONE stream at a time per context for the bounded, banded, costed and fair entry
+ * points; the scratch (as above, and a key and a band byte per request, and a flow histogram of
+ * (chunks + 1) * n_bands * n_flows 32-bit words, chunks = ceil(n_reqs / chunk) with the chunk of eppk_bounded_geometry) grows on
+ * demand, and a call that cannot have it returns EPPK_ERR_NOMEM.  The histogram scales with chunks x bands x flows, not with rows
+ * alone: 64k requests at the default chunk of 512 with 3 bands and 1 024 flows take 1.6 MB, but 8 bands x 1 024 flows under
+ * EPPK_BOUND_CHUNK=64 take 2 MiB per 64 requests.  A fair call ALWAYS takes the permutation route, also for a batch of at most one chunk (the one-launch kernels walk the rows
+ * in batch order): three launches for the fair order, three per band and round, one more.  Not here: weights per flow; turns carried
+ * from one batch to the next; a tie-break by arrival instead of flow id (a caller rotates the ids); assumed load (EPPK_ERR_ARG while
+ * it is on, as above).  Errors: as for the costed forms, and EPPK_ERR_ARG for n_flows outside 1 .. EPPK_MAX_FLOWS and for
+ * cost_flags != 0 with a null d_cost. */
+#define EPPK_MAX_FLOWS 1024u
+int eppk_fair_resolve_device(eppk_ctx* ctx, const int32_t* d_lists, const double* d_list_scores, uint32_t n_reqs, uint32_t k,
+                             const uint16_t* d_flow, uint32_t n_flows, const uint32_t* d_cost, uint32_t cost_flags,
+                             const uint8_t* d_band, const eppk_band_table* bands, const uint32_t* d_cap, uint32_t cap_all,
+                             uint32_t* d_load, int32_t* d_out_pick, double* d_out_score, uint8_t* d_out_rank, void* stream);
+int eppk_pick_fair_device(eppk_ctx* ctx, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, uint32_t k,
+                          const uint16_t* d_flow, uint32_t n_flows, const uint32_t* d_cost, const uint8_t* d_band,
+                          const eppk_band_table* bands, const uint32_t* d_cap, uint32_t cap_all, uint32_t* d_load, int32_t* d_out_pick,
+                          double* d_out_score, uint8_t* d_out_rank, void* stream);
+int eppk_pick_fair(eppk_ctx* ctx, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint16_t* flow,
+                   uint32_t n_flows, const uint32_t* cost, const uint8_t* band, const eppk_band_table* bands, const uint32_t* cap,
+                   uint32_t cap_all, uint32_t* load, int32_t* out_pick, double* out_score, uint8_t* out_rank);
+/* Over a group, as eppk_group_pick_costed: member 0 resolves; equals eppk_pick_fair on the unsharded batch bit for bit. */
+int eppk_group_pick_fair(eppk_group* g, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint16_t* flow,
+                         uint32_t n_flows, const uint32_t* cost, const uint8_t* band, const eppk_band_table* bands, const uint32_t* cap,
+                         uint32_t cap_all, uint32_t* load, int32_t* out_pick, double* out_score, uint8_t* out_rank);
+
 /* ---- adjacent host-side steps of the same path ---------------------------------------------- */
 
 /* Chain-hash a prompt into block hashes (0602-…/README.md:99): XXH64, seed 0,
