@@ -646,6 +646,66 @@ __device__ __forceinline__ uint64_t buffer_load_u64(__amdgpu_buffer_rsrc_t rs, u
   const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)voff, (int)soff, 0);
   return ((uint64_t)v.y << 32) | v.x;
 }
+__device__ __forceinline__ uint64_t u64_of(uint32_t lo, uint32_t hi) { return ((uint64_t)hi << 32) | lo; }
+
+// ---- table staging: "copy n 8-byte words from global memory to LDS by the whole workgroup", in two phases --------------------------
+// A loop `lds[i] = g[i]` compiles to load, s_waitcnt vmcnt(0), ds_write per trip: one full memory round trip each, and the first wait
+// also covers whatever the kernel issued before it.  Here a trip ISSUES up to N 16-byte loads per thread into distinct registers
+// (stage_issue) and writes LDS later (stage_write), so a caller puts the loads of several tables -- and anything else that does not
+// depend on them -- in flight before it waits for any.  Pair p (words 2p, 2p + 1) of a trip that starts at pair `first` belongs to
+// thread p - first - u * blockDim.x, u < N.  The loads go through a descriptor over exactly the n words: a pair past the end gets an
+// offset the range check drops (no branch in the load phase), its write is predicated.  ODD: n may be odd -- the last word is one more
+// 8-byte load of the first trip, the last thread's, written alone: the LDS behind the table belongs to somebody else.
+// A16: dst is 16-byte aligned (one ds_write_b128 per pair; else two 8-byte halves in one ds_write2_b64).
+template <int N, bool ODD>
+struct StageRegs { u32x4_t v[N]; u32x2_t t; };
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t stage_rsrc(const void* src, uint32_t n) {
+  const uint64_t a = (uint64_t)src;                                  // (wave-uniform, and provably so: no waterfall loop around the loads)
+  const uint64_t u = u64_of((uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a), (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32)));
+  return __builtin_amdgcn_make_buffer_rsrc((void*)u, 0, (int)(n * 8u), 0x00020000);
+}
+template <int N, bool ODD>
+__device__ __forceinline__ void stage_issue(StageRegs<N, ODD>& s, const void* src, uint32_t n, uint32_t first) {
+  constexpr uint32_t kDropped = 0x7FFFFFF0u;                         // beyond any table's last byte
+  const __amdgpu_buffer_rsrc_t rs = stage_rsrc(src, n);
+  const uint32_t npairs = n >> 1;
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+    const uint32_t p = first + (uint32_t)u * blockDim.x + threadIdx.x;
+    s.v[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(p < npairs ? p * 16u : kDropped), 0, 0);
+  }
+  // (the last thread's: every other thread is 1 MiB and more past the end -- tables are far smaller -- without a lane mask that would
+  //  have to live until the write)
+  if constexpr (ODD) s.t = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)((((n & 1u) && first == 0u) ? (n - 1u) * 8u : kDropped) + ((blockDim.x - 1u - threadIdx.x) << 20)), 0, 0);
+}
+template <bool A16, int N, bool ODD>
+__device__ __forceinline__ void stage_write(const StageRegs<N, ODD>& s, void* dst, uint32_t n, uint32_t first) {
+  const uint32_t npairs = n >> 1;
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+    const uint32_t p = first + (uint32_t)u * blockDim.x + threadIdx.x;
+    if (p < npairs) {
+      if constexpr (A16) ((u32x4_t*)dst)[p] = s.v[u];
+      else { ((uint64_t*)dst)[2u * p] = u64_of(s.v[u].x, s.v[u].y); ((uint64_t*)dst)[2u * p + 1u] = u64_of(s.v[u].z, s.v[u].w); }
+    }
+  }
+  if constexpr (ODD)
+    if ((n & 1u) && first == 0u && threadIdx.x == blockDim.x - 1u) ((uint64_t*)dst)[n - 1u] = u64_of(s.t.x, s.t.y);
+}
+// the trips from pair `first` on (none where the caller's own first trip covered the table)
+template <bool A16, int N>
+__device__ __forceinline__ void stage_rest(void* dst, const void* src, uint32_t n, uint32_t first) {
+  for (; first < (n >> 1); first += (uint32_t)N * blockDim.x) {
+    StageRegs<N, false> s;
+    stage_issue(s, src, n, first);
+    stage_write<A16>(s, dst, n, first);
+  }
+}
+// n16 x 16 zero bytes at an 8-byte aligned LDS address, by the whole workgroup
+__device__ __forceinline__ void lds_zero16(void* dst, uint32_t n16) {
+  for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) { ((uint64_t*)dst)[2u * i] = 0ull; ((uint64_t*)dst)[2u * i + 1u] = 0ull; }
+}
+
 // Home bucket of q.h (q.h must already be 0 in lanes without a key).
 __device__ __forceinline__ void pair_probe_prepare(const KIndex& ix, ReqRegs& q) { q.bkt = home_bucket(q.h, ix.shift); }
 // Issue the two 16-byte loads of this lane's half of the home bucket (rk = buffer descriptor of the index allocation).
@@ -661,8 +721,6 @@ __device__ __forceinline__ void pair_probe_issue(__amdgpu_buffer_rsrc_t rk, uint
   }
 #endif
 }
-
-__device__ __forceinline__ uint64_t u64_of(uint32_t lo, uint32_t hi) { return ((uint64_t)hi << 32) | lo; }
 
 // Position (0..3) of h among this lane's 4 bucket words, 4 if absent.  Words 0..2 of a bucket -- the even lane's first three -- are
 // flags and meta dwords, not keys (kBucket).
@@ -1011,15 +1069,29 @@ __device__ __forceinline__ void pick_fast_body(const uint32_t vblock, const uint
   uint32_t* s_hist_all = (uint32_t*)(s_scr_all + (size_t)(blockDim.x >> 6) * 64u);    // [waves][J * 16] dwords: one byte per pod
   const bool use_lists = SPARSE && ix.lists != nullptr;
   if (!(RESIDENT && tail)) {      // (the histogram and the scratch words are all-zero between two requests, so also between two doorbells)
-    for (uint32_t i = threadIdx.x; i < sn.J * 64u; i += blockDim.x) s_base[i] = sn.base[i];
-    if (threadIdx.x == 0u) { s_lw[0] = tl.lw[0]; s_lw[1] = tl.lw[1]; s_lw[2] = tl.lw[2]; s_lw[3] = tl.lw[3]; }   // (no dynamic index into the argument struct: that costs scratch)
-    if (GEN)
-      for (uint32_t i = threadIdx.x; i < sn.J * 64u; i += blockDim.x) { s_post0[i] = sn.post[0][i]; s_post1[i] = sn.post[1][i]; }
-    if (pterm_tab)
-      for (uint32_t i = threadIdx.x; i < pwn; i += blockDim.x) s_pterm[i] = sn.pterm[i];
-    if (use_lists)
-      for (uint32_t i = threadIdx.x; i < (blockDim.x >> 6) * sn.J * 16u; i += blockDim.x) s_hist_all[i] = 0u;
-    for (uint32_t i = threadIdx.x; i < (blockDim.x >> 6) * 64u; i += blockDim.x) s_scr_all[i] = (LW)0;
+    // every table's first trip is in flight before anything waits (stage_issue); the zeroing runs under the loads.  s_post0 and what
+    // follows it are 8-byte aligned only: pwn may be odd.
+    const double lw0 = tl.lw[0], lw1 = tl.lw[1], lw2 = tl.lw[2], lw3 = tl.lw[3];   // (no dynamic index into the argument struct: that costs scratch)
+    constexpr int kNB = 4, kNP = 2;
+    const uint32_t nbase = sn.J * 64u;
+    StageRegs<kNB, false> gb;
+    StageRegs<kNP, true> gp;
+    StageRegs<kNP, false> g0, g1;
+    stage_issue(gb, sn.base, nbase, 0u);
+    if constexpr (pterm_tab) stage_issue(gp, sn.pterm, pwn, 0u);
+    if constexpr (GEN) { stage_issue(g0, sn.post[0], nbase, 0u); stage_issue(g1, sn.post[1], nbase, 0u); }
+    // (the scratch words and, behind them, the histogram: multiples of 16 bytes both)
+    lds_zero16(s_scr_all, (blockDim.x >> 6) * (4u * (uint32_t)sizeof(LW) + (use_lists ? sn.J * 4u : 0u)));
+    if (threadIdx.x == 0u) { s_lw[0] = lw0; s_lw[1] = lw1; s_lw[2] = lw2; s_lw[3] = lw3; }
+    stage_write<true>(gb, s_base, nbase, 0u);
+    if constexpr (pterm_tab) stage_write<true>(gp, s_pterm, pwn, 0u);
+    if constexpr (GEN) { stage_write<false>(g0, s_post0, nbase, 0u); stage_write<false>(g1, s_post1, nbase, 0u); }
+    stage_rest<true, kNB>(s_base, sn.base, nbase, (uint32_t)kNB * blockDim.x);
+    if constexpr (pterm_tab) stage_rest<true, kNB>(s_pterm, sn.pterm, pwn, (uint32_t)kNP * blockDim.x);
+    if constexpr (GEN) {
+      stage_rest<false, kNB>(s_post0, sn.post[0], nbase, (uint32_t)kNP * blockDim.x);
+      stage_rest<false, kNB>(s_post1, sn.post[1], nbase, (uint32_t)kNP * blockDim.x);
+    }
   }
   __syncthreads();
 
@@ -1873,8 +1945,13 @@ __global__ __launch_bounds__(EPPK_FAST_MAX_THREADS, EPPK_MIN_WAVES) void pick_fa
 #ifndef EPPK_QUAD_PIPE_KEYS
 #define EPPK_QUAD_PIPE_KEYS 1   // 1: the key gather of the next block is in flight while this one is evaluated
 #endif
+#ifndef EPPK_QUAD_KEYS_EARLY
+#define EPPK_QUAD_KEYS_EARLY 0  // 1: a launched kernel gathers its first block's keys while the table staging loads are in flight, not behind
+                                // the barrier (measured: it gives back what issuing the staging loads together gains,
+                                // profiles/r07_staging_before_after.txt)
+#endif
 #ifndef EPPK_QUAD_PARK
-#define EPPK_QUAD_PARK 1        // 0: masked single picks defer the rows they cannot score from base[] and the top table (A/B runs)
+#define EPPK_QUAD_PARK 1       // 0: masked single picks defer the rows they cannot score from base[] and the top table (A/B runs)
 #endif
 #ifndef EPPK_QUAD_WAVES
 #define EPPK_QUAD_WAVES 4       // wavefronts per SIMD the register allocation aims at (<= 128 VGPRs)
@@ -2893,16 +2970,37 @@ __device__ __forceinline__ uint32_t pick_quad_body(const uint32_t vblock, const 
   issue_row(gwave, qa);                                              // the first rows come from HBM: in flight while the tables are staged
   if (!RESIDENT || gwave + nwaves < nblk) issue_row(gwave + nwaves, qb);   // (RESIDENT: rows cross PCIe -- no load that nobody waits for)
   if constexpr (!RESIDENT) {                                         // (RESIDENT: the tables are in LDS already and stay there between doorbells)
+    // The tables: every load of the first trip -- 4 + 2 (+ 1: pwn may be odd) per thread, the whole of both tables at the headline shape
+    // with 512 threads -- is issued before anything waits, behind the rows (vmcnt retires in order: the rows land first).
+    // EPPK_QUAD_KEYS_EARLY: the first block's key gather goes out while they are in flight -- it needs the rows alone, and ds_bpermute
+    // touches no LDS storage (the crossbar scratch is first written in process(), behind the barrier).
+    // (no dynamic index into the argument struct; ahead of the loads: no argument word is fetched between them; the LAST thread: thread
+    //  0's lane mask would be kept, spilled, for the report at the kernel's end)
+    if (threadIdx.x == blockDim.x - 1u) { s_lw[0] = tl.lw[0]; s_lw[1] = tl.lw[1]; s_lw[2] = tl.lw[2]; s_lw[3] = tl.lw[3]; }
+    constexpr int kNB = 4, kNP = 2;
+    const uint32_t nbase = sn.J * 64u;
+    StageRegs<kNB, false> gb;
+    StageRegs<kNP, true> gp;
 #ifndef EPPK_DBGQ_NO_STAGE  // (defined: timing experiment only, wrong results: base[] is not staged)
-    for (uint32_t i = threadIdx.x; i < sn.J * 32u; i += blockDim.x) ((double2*)s_base)[i] = ((const double2*)sn.base)[i];   // (16 bytes per load: every
-                                                                     // vector memory instruction costs the CU's address unit ~16 clocks)
+    stage_issue(gb, sn.base, nbase, 0u);                             // (16 bytes per load: every vector memory instruction costs the CU's
+                                                                     // address unit ~16 clocks)
 #endif
-    if (threadIdx.x == 0u) { s_lw[0] = tl.lw[0]; s_lw[1] = tl.lw[1]; s_lw[2] = tl.lw[2]; s_lw[3] = tl.lw[3]; }   // (no dynamic index into the argument struct)
-    for (uint32_t i = threadIdx.x; i < pwn / 2u; i += blockDim.x) ((double2*)s_pterm)[i] = ((const double2*)sn.pterm)[i];
-    if ((pwn & 1u) && threadIdx.x == 0u) s_pterm[pwn - 1u] = sn.pterm[pwn - 1u];
-    for (uint32_t i = threadIdx.x; i < (blockDim.x >> 4) * bits_dw; i += blockDim.x) s_bits_all[i] = 0u;
-    if (MASKED)
-      for (uint32_t i = threadIdx.x; i < 192u; i += blockDim.x) s_nat[i] = sn.nat[i];
+    stage_issue(gp, sn.pterm, pwn, 0u);
+    StageRegs<1, false> gn;
+    if constexpr (MASKED) stage_issue(gn, sn.nat, 192u, 0u);
+#if EPPK_QUAD_PIPE_KEYS && EPPK_QUAD_KEYS_EARLY
+    if (!idle) issue_keys(qa, pb);
+#endif
+    lds_zero16(s_bits_all, (blockDim.x >> 6) * bits_dw);             // (dwords / 4; 8-byte aligned where pwn is odd)
+#ifndef EPPK_DBGQ_NO_STAGE
+    stage_write<true>(gb, s_base, nbase, 0u);
+#endif
+    stage_write<true>(gp, s_pterm, pwn, 0u);
+#ifndef EPPK_DBGQ_NO_STAGE
+    stage_rest<true, kNB>(s_base, sn.base, nbase, (uint32_t)kNB * blockDim.x);
+#endif
+    stage_rest<true, kNB>(s_pterm, sn.pterm, pwn, (uint32_t)kNP * blockDim.x);
+    if constexpr (MASKED) { stage_write<false>(gn, s_nat, 192u, 0u); stage_rest<false, 1>(s_nat, sn.nat, 192u, blockDim.x); }
     __syncthreads();
   }
   if (idle) {
@@ -2910,7 +3008,7 @@ __device__ __forceinline__ uint32_t pick_quad_body(const uint32_t vblock, const 
   }
   if (!idle) {
 #if EPPK_QUAD_PIPE_KEYS
-    issue_keys(qa, pb);
+    if (RESIDENT || !EPPK_QUAD_KEYS_EARLY) issue_keys(qa, pb);
 #endif
     for (uint32_t blk = gwave; blk < nblk; blk += 2u * nwaves) {
       process(blk, qa, qb, pb);
