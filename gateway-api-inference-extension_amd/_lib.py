@@ -41,6 +41,7 @@ SYMBOLS = [
     "eppk_banded_resolve_device", "eppk_pick_banded_device", "eppk_pick_banded", "eppk_group_pick_banded",
     "eppk_costed_resolve_device", "eppk_pick_costed_device", "eppk_pick_costed", "eppk_group_pick_costed",
     "eppk_fair_resolve_device", "eppk_pick_fair_device", "eppk_pick_fair", "eppk_group_pick_fair",
+    "eppk_wfair_resolve_device", "eppk_pick_wfair_device", "eppk_pick_wfair", "eppk_group_pick_wfair", "eppk_fair_turns_rebase",
     "eppk_group_create", "eppk_group_destroy", "eppk_group_last_error", "eppk_group_size", "eppk_group_ctx", "eppk_group_ranks_seen",
     "eppk_group_set_min_shard", "eppk_group_snapshot_publish", "eppk_group_index_clear", "eppk_group_index_insert",
     "eppk_group_index_remove_pod", "eppk_group_index_advance_epoch", "eppk_group_index_evict_older", "eppk_group_pick_batch",
@@ -178,6 +179,11 @@ def load_library() -> C.CDLL:
     lib.eppk_pick_fair_device.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp, vp]
     lib.eppk_pick_fair.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp]
     lib.eppk_group_pick_fair.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp]
+    lib.eppk_wfair_resolve_device.argtypes = [vp, vp, vp, u32, u32, vp, u32, vp, vp, vp, u32, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp, vp]
+    lib.eppk_pick_wfair_device.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp, vp]
+    lib.eppk_pick_wfair.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp]
+    lib.eppk_group_pick_wfair.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp]
+    lib.eppk_fair_turns_rebase.argtypes = [vp, vp, u32, u32, u32]
     lib.eppk_group_create.argtypes = [C.POINTER(Cfg), C.POINTER(i32), u32, u32, C.POINTER(vp)]
     lib.eppk_group_destroy.argtypes = [vp]
     lib.eppk_group_destroy.restype = None

@@ -13,6 +13,7 @@
 #include "eppk_banded.hip.h"
 #include "eppk_costed.hip.h"
 #include "eppk_fair.hip.h"
+#include "eppk_wfair.hip.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -231,6 +232,8 @@ struct eppk_ctx {
   DBuf<uint16_t> d_fr_key;                                  // a key per request (band * n_flows + flow, or 0xFFFF: not in the order)
   DBuf<uint8_t> d_fr_band;                                  // the effective band byte per request: the band, or 0xFF for a row that is not in the order
   DBuf<uint16_t> d_fr_flow;                                 // flow ids of the host forms
+  // ... with weights per flow and turns carried between batches (SEMANTICS.md §3h; eppk_wfair.hip.h): the fair picker's buffers, and
+  DBuf<uint32_t> d_wf;                                      // kWfairWords words: t[G] | taken[G] | w[n_flows] of the call, then the host forms' turns and weights
 
   // measurement
   bool prof = false;
@@ -3569,6 +3572,230 @@ int eppk_pick_fair(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint64_
   return fair_host_finish(c, c->d_tk_pick, c->d_tk_score, n_reqs, k, flow, n_flows, cost, band, counts, tab, cap, cap_all, load, out_pick, out_score, out_rank);
 }
 
+// ---- ... with weights per flow and turns carried between batches (SEMANTICS.md §3h; eppk_wfair.hip.h) ---------------------------------
+
+namespace {
+
+int wfair_check(eppk_ctx* c, const char* who, uint32_t k, const eppk_band_table* t, uint32_t n_flows, const void* cost, uint32_t cost_flags,
+                eppk::BandTab* tab) {
+  return fair_check(c, who, k, t, n_flows, cost, cost_flags, tab);
+}
+
+// As fair_host_counts, and the weights: a row whose flow has weight 0 is refused like a row whose flow is out of range (the lowest bad
+// row is named), and behind the rows a zero weight anywhere in the array, naming the flow.
+int wfair_host_counts(eppk_ctx* c, const char* who, const uint8_t* band, const uint16_t* flow, uint32_t n_flows, const uint16_t* weight, const uint32_t* cost,
+                      uint32_t n_reqs, uint32_t n_bands, uint32_t counts[EPPK_MAX_BANDS]) {
+  for (uint32_t b = 0; b < EPPK_MAX_BANDS; ++b) counts[b] = 0u;
+  for (uint32_t r = 0; r < n_reqs; ++r) {
+    const uint32_t b = band ? band[r] : 0u, f = flow ? flow[r] : 0u;
+    if (b >= n_bands)
+      return fail(c, EPPK_ERR_ARG, std::string(who) + ": request row " + std::to_string(r) + " names band " + std::to_string(b) + " of " + std::to_string(n_bands));
+    if (f >= n_flows)
+      return fail(c, EPPK_ERR_ARG, std::string(who) + ": request row " + std::to_string(r) + " names flow " + std::to_string(f) + " of " + std::to_string(n_flows));
+    if (weight && weight[f] == 0u)
+      return fail(c, EPPK_ERR_ARG, std::string(who) + ": request row " + std::to_string(r) + " names flow " + std::to_string(f) + " of weight 0");
+    if (cost && cost[r] - 1u >= EPPK_MAX_COST)
+      return fail(c, EPPK_ERR_ARG, std::string(who) + ": request row " + std::to_string(r) + " has cost " + std::to_string(cost[r]) + " (1.." +
+                                       std::to_string(EPPK_MAX_COST) + ")");
+    ++counts[b];
+  }
+  if (weight)
+    for (uint32_t f = 0; f < n_flows; ++f)
+      if (weight[f] == 0u) return fail(c, EPPK_ERR_ARG, std::string(who) + ": flow " + std::to_string(f) + " has weight 0");
+  return EPPK_OK;
+}
+
+int wfair_scratch(eppk_ctx* c) { return ctx_grow(c, (size_t)eppk::kWfairWords, {{c->d_wf, sizeof(uint32_t), "weighted fair picker: turns and weights"}}); }
+
+// The launches of the weighted fair resolve on `st` (arguments checked by the caller; n_reqs != 0): fair_resolve with the weighted order
+// (wfair_stage_kernel, wfair_hist_kernel, fair_offsets_kernel, wfair_scatter_kernel) in front of the same round and finish kernels, and
+// with a d_turns the carry behind the finish (wfair_taken_kernel, wfair_carry_kernel: d_turns is written by the last launch on `st`).
+int wfair_resolve(eppk_ctx* c, const int32_t* d_lists, const double* d_scores, uint32_t n_reqs, uint32_t k, const uint16_t* d_flow, uint32_t n_flows,
+                  const uint16_t* d_weight, uint32_t* d_turns, const uint32_t* d_cost, uint32_t cost_flags, const uint8_t* d_band, const eppk::BandTab& tab,
+                  const uint32_t* counts, const uint32_t* d_cap, uint32_t cap_all, uint32_t* d_load, int32_t* d_out_pick, double* d_out_score,
+                  uint8_t* d_out_rank, hipStream_t st) {
+  const uint32_t P = c->n_pods, chunk = c->bound_chunk;
+  const eppk::CostOf cost{d_cost, k, cost_flags & EPPK_COST_PER_ENTRY};
+  const size_t G = (size_t)tab.n_bands * n_flows;
+  int rc;
+  uint8_t* state = d_out_rank;
+  if (!state) {
+    if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_bd_state, 1u, "bounded picker: request states"}}))) return rc;
+    state = c->d_bd_state;
+  }
+  const uint32_t n_chunks = (uint32_t)(((uint64_t)n_reqs + chunk - 1u) / chunk);
+  if ((rc = bounded_pod_scratch(c))) return rc;
+  if ((rc = ctx_grow(c, (size_t)n_chunks * P, {{c->d_bd_hist, sizeof(uint32_t), "bounded picker: bid histogram"}}))) return rc;
+  if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_bn_perm, sizeof(uint32_t), "banded picker: band order"}}))) return rc;
+  if ((rc = ctx_grow(c, eppk::kBandSegWords + (size_t)n_chunks * EPPK_MAX_BANDS, {{c->d_bn_bh, sizeof(uint32_t), "banded picker: band histogram"}}))) return rc;
+  if ((rc = ctx_grow(c, (size_t)EPPK_MAX_PODS, {{c->d_cs_acc, sizeof(uint32_t), "costed picker: takers' totals"}}))) return rc;
+  if ((rc = ctx_grow(c, G + (size_t)n_chunks * G, {{c->d_fr_fh, sizeof(uint32_t), "fair picker: flow histogram"}}))) return rc;
+  if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_fr_key, sizeof(uint16_t), "fair picker: keys"}, {c->d_fr_band, 1u, "fair picker: effective bands"}}))) return rc;
+  if ((rc = wfair_scratch(c))) return rc;
+  const size_t lds = eppk::wfair_lds_bytes(G, n_flows);
+  if (lds > 64u * 1024u) {   // above the default dynamic-LDS limit: raised once, to the largest request the kernel can make (occupancy_of, g_lds_limit)
+    int per_cu = 0;
+    if ((rc = occupancy_of(c, (const void*)eppk::wfair_scatter_kernel, 64u, eppk::kWfairMaxLds, &per_cu))) return rc;
+  }
+  uint32_t* seg = c->d_bn_bh;
+  uint32_t* cnt = c->d_fr_fh;
+  uint32_t* fh = c->d_fr_fh + G;
+  uint32_t* perm = c->d_bn_perm;
+  uint32_t* room = c->d_bd_pods;
+  uint32_t* acc = c->d_cs_acc;
+  uint32_t* t_own = c->d_wf + eppk::kWfairT;
+  uint32_t* taken = c->d_wf + eppk::kWfairTaken;
+  uint32_t* w_own = c->d_wf + eppk::kWfairW;
+  const uint8_t* eband = c->d_fr_band;
+  uint32_t* load = d_load;
+  if (!load) {
+    load = c->d_bd_pods + EPPK_MAX_PODS;
+    HIPCHK(c, hipMemsetAsync(load, 0, (size_t)EPPK_MAX_PODS * sizeof(uint32_t), st));
+  }
+  if (d_cost) HIPCHK(c, hipMemsetAsync(acc, 0, (size_t)EPPK_MAX_PODS * sizeof(uint32_t), st));
+  HIPCHK(c, hipMemsetAsync(seg, 0, (size_t)eppk::kBandSegWords * sizeof(uint32_t), st));
+  HIPCHK(c, hipMemsetAsync(state, (int)eppk::kBoundUnassigned, n_reqs, st));
+  // grid-stride loops as wide as the CUs this context may use (EPPK_MAX_CU): the results do not depend on the width
+  const uint32_t wide = (uint32_t)c->num_cu * 4u;
+  const uint32_t chunk_grid = n_chunks < wide ? n_chunks : wide;
+  const uint32_t pod_wgs = (P + eppk::kBoundScanPods - 1u) / eppk::kBoundScanPods, pod_grid = pod_wgs < wide ? pod_wgs : wide;
+  const uint32_t key_wgs = (uint32_t)((G + eppk::kBoundScanPods - 1u) / eppk::kBoundScanPods), key_grid = key_wgs < wide ? key_wgs : wide;
+  const uint32_t row_wgs = (uint32_t)(((uint64_t)n_reqs + eppk::kBoundThreads - 1u) / eppk::kBoundThreads), row_grid = row_wgs < wide * 2u ? row_wgs : wide * 2u;
+  const uint32_t gk_wgs = (uint32_t)((G + eppk::kBoundThreads - 1u) / eppk::kBoundThreads), gk_grid = gk_wgs < wide ? gk_wgs : wide;
+  hipLaunchKernelGGL(eppk::wfair_stage_kernel, dim3(gk_grid), dim3(eppk::kBoundThreads), 0, st, d_weight, (const uint32_t*)d_turns, tab.n_bands, n_flows, w_own, t_own, taken);
+  hipLaunchKernelGGL(eppk::wfair_hist_kernel, dim3(chunk_grid), dim3(eppk::kBoundThreads), 0, st, d_band, d_flow, (const uint32_t*)w_own, n_reqs, tab.n_bands, n_flows,
+                     chunk, n_chunks, fh, (uint16_t*)c->d_fr_key, (uint8_t*)c->d_fr_band);
+  hipLaunchKernelGGL(eppk::fair_offsets_kernel, dim3(key_grid), dim3(eppk::kBoundScanSegs * eppk::kBoundScanPods), 0, st, fh, n_chunks, tab.n_bands, n_flows, cnt, seg);
+  hipLaunchKernelGGL(eppk::wfair_scatter_kernel, dim3(chunk_grid), dim3(64), lds, st, (const uint16_t*)c->d_fr_key, n_reqs, tab.n_bands, n_flows, chunk, n_chunks,
+                     (const uint32_t*)fh, (const uint32_t*)cnt, (const uint32_t*)seg, (const uint32_t*)t_own, (const uint32_t*)w_own, perm);
+  if (P) for (uint32_t b = 0; b < tab.n_bands; ++b) {
+    uint32_t band_grid = chunk_grid;
+    if (counts) {
+      if (!counts[b]) continue;
+      const uint32_t band_chunks = (uint32_t)(((uint64_t)counts[b] + chunk - 1u) / chunk);
+      band_grid = band_chunks < wide ? band_chunks : wide;
+    }
+    const eppk::CostRoomGlobal room_now{d_cap, cap_all, tab.reserve[b], load, acc};
+    for (uint32_t j = 0; j < k; ++j) {
+      if (d_cost) {
+        hipLaunchKernelGGL(eppk::costed_count_kernel, dim3(band_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, k, j, P, chunk, (const uint32_t*)seg, b,
+                           (const uint32_t*)perm, cost, room_now, state, c->d_bd_hist);
+        hipLaunchKernelGGL(eppk::costed_scan_kernel, dim3(pod_grid), dim3(eppk::kBoundScanSegs * eppk::kBoundScanPods), 0, st, c->d_bd_hist, chunk,
+                           (const uint32_t*)seg, b, P, d_cap, cap_all, tab.reserve[b], load, acc, room);
+        hipLaunchKernelGGL(eppk::costed_assign_kernel, dim3(band_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, d_scores, k, j, P, chunk, (const uint32_t*)seg,
+                           b, (const uint32_t*)perm, cost, (const uint32_t*)c->d_bd_hist, (const uint32_t*)room, acc, state, d_out_pick, d_out_score);
+      } else {
+        hipLaunchKernelGGL(eppk::banded_count_kernel, dim3(band_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, k, j, P, chunk, (const uint32_t*)seg, b,
+                           (const uint32_t*)perm, (const uint8_t*)state, c->d_bd_hist);
+        hipLaunchKernelGGL(eppk::banded_scan_kernel, dim3(pod_grid), dim3(eppk::kBoundScanSegs * eppk::kBoundScanPods), 0, st, c->d_bd_hist, chunk,
+                           (const uint32_t*)seg, b, P, d_cap, cap_all, tab.reserve[b], load, room);
+        hipLaunchKernelGGL(eppk::banded_assign_kernel, dim3(band_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, d_scores, k, j, P, chunk, (const uint32_t*)seg,
+                           b, (const uint32_t*)perm, (const uint32_t*)c->d_bd_hist, (const uint32_t*)room, state, d_out_pick, d_out_score);
+      }
+    }
+  }
+  if (d_cost)
+    hipLaunchKernelGGL(eppk::costed_finish_kernel, dim3(row_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, d_scores, n_reqs, k, P, cost, eband, tab.n_bands,
+                       tab.spill, load, (const uint32_t*)acc, state, d_out_pick, d_out_score, c->d_status);
+  else
+    hipLaunchKernelGGL(eppk::banded_finish_kernel, dim3(row_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, d_scores, n_reqs, k, P, eband, tab.n_bands, tab.spill,
+                       load, state, d_out_pick, d_out_score, c->d_status);
+  if (d_turns) {
+    hipLaunchKernelGGL(eppk::wfair_taken_kernel, dim3(chunk_grid), dim3(eppk::kBoundThreads), 0, st, (const uint16_t*)c->d_fr_key, (const int32_t*)d_out_pick, n_reqs,
+                       tab.n_bands, n_flows, chunk, n_chunks, taken);
+    hipLaunchKernelGGL(eppk::wfair_carry_kernel, dim3(gk_grid), dim3(eppk::kBoundThreads), 0, st, (const uint32_t*)t_own, (const uint32_t*)taken, tab.n_bands, n_flows,
+                       d_turns);
+  }
+  HIPCHK(c, hipGetLastError());
+  return EPPK_OK;
+}
+
+// Band bytes, flow ids, costs, weights and turns up (checked and counted by wfair_host_counts), then as bounded_host_finish; the turns
+// come down behind the resolve, in front of the wait.
+int wfair_host_finish(eppk_ctx* c, const int32_t* d_lists, const double* d_scores, uint32_t n_reqs, uint32_t k, const uint16_t* flow, uint32_t n_flows,
+                      const uint16_t* weight, uint32_t* turns, const uint32_t* cost, const uint8_t* band, const uint32_t* counts, const eppk::BandTab& tab,
+                      const uint32_t* cap, uint32_t cap_all, uint32_t* load, int32_t* out_pick, double* out_score, uint8_t* out_rank) {
+  int rc;
+  if (band) {
+    if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_bn_band, 1u, "banded picker: bands"}}))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_bn_band, band, n_reqs, hipMemcpyHostToDevice, c->stream));
+  }
+  if (flow) {
+    if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_fr_flow, sizeof(uint16_t), "fair picker: flows"}}))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_fr_flow, flow, (size_t)n_reqs * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+  }
+  if (cost) {
+    if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_cs_cost, sizeof(uint32_t), "costed picker: costs"}}))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_cs_cost, cost, (size_t)n_reqs * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  }
+  if ((rc = wfair_scratch(c))) return rc;
+  const size_t G = (size_t)tab.n_bands * n_flows;
+  uint32_t* d_turns = turns ? c->d_wf + eppk::kWfairHostT : nullptr;
+  uint16_t* d_weight = weight ? (uint16_t*)(c->d_wf + eppk::kWfairHostW) : nullptr;
+  if (turns) HIPCHK(c, hipMemcpyAsync(d_turns, turns, G * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  if (weight) HIPCHK(c, hipMemcpyAsync(d_weight, weight, (size_t)n_flows * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+  return bounded_host_around(c, n_reqs, cap, load, out_pick, out_score, out_rank,
+                             [&](const uint32_t* d_cap, uint32_t* d_load, int32_t* d_pick, double* d_score, uint8_t* d_rank) {
+                               const int rcr = wfair_resolve(c, d_lists, d_scores, n_reqs, k, flow ? (const uint16_t*)c->d_fr_flow : nullptr, n_flows, d_weight,
+                                                             d_turns, cost ? (const uint32_t*)c->d_cs_cost : nullptr, 0u,
+                                                             band ? (const uint8_t*)c->d_bn_band : nullptr, tab, counts, d_cap, cap_all, d_load, d_pick, d_score,
+                                                             d_rank, c->stream);
+                               if (rcr) return rcr;
+                               if (turns) HIPCHK(c, hipMemcpyAsync(turns, d_turns, G * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+                               return (int)EPPK_OK;
+                             });
+}
+
+}  // namespace
+
+int eppk_wfair_resolve_device(eppk_ctx* c, const int32_t* d_lists, const double* d_list_scores, uint32_t n_reqs, uint32_t k, const uint16_t* d_flow,
+                              uint32_t n_flows, const uint16_t* d_weight, uint32_t* d_turns, const uint32_t* d_cost, uint32_t cost_flags, const uint8_t* d_band,
+                              const eppk_band_table* bands, const uint32_t* d_cap, uint32_t cap_all, uint32_t* d_load, int32_t* d_out_pick, double* d_out_score,
+                              uint8_t* d_out_rank, void* stream) {
+  if (!c || ((!d_lists || !d_out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_wfair_resolve_device: null argument");
+  eppk::BandTab tab;
+  const int rcc = wfair_check(c, "eppk_wfair_resolve_device", k, bands, n_flows, d_cost, cost_flags, &tab);
+  if (rcc) return rcc;
+  if (n_reqs == 0) return EPPK_OK;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  return wfair_resolve(c, d_lists, d_list_scores, n_reqs, k, d_flow, n_flows, d_weight, d_turns, d_cost, cost_flags, d_band, tab, nullptr, d_cap, cap_all, d_load,
+                       d_out_pick, d_out_score, d_out_rank, stream ? (hipStream_t)stream : c->stream);
+}
+
+int eppk_pick_wfair_device(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, uint32_t k, const uint16_t* d_flow, uint32_t n_flows,
+                           const uint16_t* d_weight, uint32_t* d_turns, const uint32_t* d_cost, const uint8_t* d_band, const eppk_band_table* bands,
+                           const uint32_t* d_cap, uint32_t cap_all, uint32_t* d_load, int32_t* d_out_pick, double* d_out_score, uint8_t* d_out_rank,
+                           void* stream) {
+  if (!c || ((!d_reqs || !d_out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_wfair_device: null argument");
+  eppk::BandTab tab;
+  int rc = wfair_check(c, "eppk_pick_wfair_device", k, bands, n_flows, d_cost, 0u, &tab);
+  if (rc) return rc;
+  if (n_reqs == 0) return EPPK_OK;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if ((rc = bounded_lists(c, n_reqs))) return rc;
+  if ((rc = eppk_pick_topk_device(c, d_reqs, n_reqs, d_cand_mask, k, c->d_bd_list, c->d_bd_lscore, stream))) return rc;
+  return wfair_resolve(c, c->d_bd_list, c->d_bd_lscore, n_reqs, k, d_flow, n_flows, d_weight, d_turns, d_cost, 0u, d_band, tab, nullptr, d_cap, cap_all, d_load,
+                       d_out_pick, d_out_score, d_out_rank, stream ? (hipStream_t)stream : c->stream);
+}
+
+int eppk_pick_wfair(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint16_t* flow, uint32_t n_flows,
+                    const uint16_t* weight, uint32_t* turns, const uint32_t* cost, const uint8_t* band, const eppk_band_table* bands, const uint32_t* cap,
+                    uint32_t cap_all, uint32_t* load, int32_t* out_pick, double* out_score, uint8_t* out_rank) {
+  if (!c || ((!reqs || !out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_wfair: null argument");
+  eppk::BandTab tab;
+  int rc = wfair_check(c, "eppk_pick_wfair", k, bands, n_flows, cost, 0u, &tab);
+  if (rc) return rc;
+  if (n_reqs > c->cfg.max_batch) return fail(c, EPPK_ERR_LIMIT, "eppk_pick_wfair: n_reqs > max_batch");
+  uint32_t counts[EPPK_MAX_BANDS];
+  if ((rc = wfair_host_counts(c, "eppk_pick_wfair", band, flow, n_flows, weight, cost, n_reqs, tab.n_bands, counts))) return rc;
+  if (n_reqs == 0) return EPPK_OK;
+  if ((rc = validate_rows(c, "eppk_pick_wfair", reqs, n_reqs))) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if ((rc = bounded_host_lists(c, reqs, n_reqs, cand_mask, k))) return rc;
+  return wfair_host_finish(c, c->d_tk_pick, c->d_tk_score, n_reqs, k, flow, n_flows, weight, turns, cost, band, counts, tab, cap, cap_all, load, out_pick, out_score,
+                           out_rank);
+}
+
 // ---- on-device prompt hashing ------------------------------------------------------------------------
 
 int eppk_hash_prompts_device(eppk_ctx* c, const void* d_prompts, uint64_t prompt_stride, const uint32_t* d_prompt_len,
@@ -4276,6 +4503,33 @@ int eppk_group_pick_fair(eppk_group* g, const void* reqs, uint32_t n_reqs, const
     return gfail(g, EPPK_ERR_DEVICE, "eppk_group_pick_fair: upload failed");
   if ((rc = fair_host_finish(c0, c0->d_bd_list, c0->d_bd_lscore, n_reqs, k, flow, n_flows, cost, band, counts, tab, cap, cap_all, load, out_pick, out_score,
                              out_rank)))
+    return mfail(rc);
+  return EPPK_OK;
+}
+
+int eppk_group_pick_wfair(eppk_group* g, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint16_t* flow, uint32_t n_flows,
+                          const uint16_t* weight, uint32_t* turns, const uint32_t* cost, const uint8_t* band, const eppk_band_table* bands, const uint32_t* cap,
+                          uint32_t cap_all, uint32_t* load, int32_t* out_pick, double* out_score, uint8_t* out_rank) {
+  if (!g || ((!reqs || !out_pick) && n_reqs)) return gfail(g, EPPK_ERR_ARG, "eppk_group_pick_wfair: null argument");
+  eppk_ctx* c0 = g->ctx[0];
+  eppk::BandTab tab;
+  uint32_t counts[EPPK_MAX_BANDS];
+  int rc = wfair_check(c0, "eppk_group_pick_wfair", k, bands, n_flows, cost, 0u, &tab);
+  if (!rc) rc = wfair_host_counts(c0, "eppk_group_pick_wfair", band, flow, n_flows, weight, cost, n_reqs, tab.n_bands, counts);
+  if (rc) return gfail(g, rc, eppk_last_error(c0));
+  // as eppk_group_pick_bounded: the lists of the whole batch on the host, then ONE resolve on member 0
+  std::vector<int32_t> lists((size_t)n_reqs * k);
+  std::vector<double> totals((size_t)n_reqs * k);
+  if ((rc = group_topk(g, "eppk_group_pick_wfair", reqs, n_reqs, cand_mask, k, false, 0ull, lists.data(), totals.data()))) return rc;
+  if (n_reqs == 0) return EPPK_OK;
+  auto mfail = [&](int code) { return gfail(g, code, "device " + std::to_string(g->dev[0]) + ": " + eppk_last_error(c0)); };
+  if (hipSetDevice(g->dev[0]) != hipSuccess) return gfail(g, EPPK_ERR_DEVICE, "eppk_group_pick_wfair: hipSetDevice failed");
+  if ((rc = bounded_lists(c0, n_reqs))) return mfail(rc);
+  if (hipMemcpyAsync(c0->d_bd_list, lists.data(), lists.size() * 4u, hipMemcpyHostToDevice, c0->stream) != hipSuccess ||
+      hipMemcpyAsync(c0->d_bd_lscore, totals.data(), totals.size() * 8u, hipMemcpyHostToDevice, c0->stream) != hipSuccess)
+    return gfail(g, EPPK_ERR_DEVICE, "eppk_group_pick_wfair: upload failed");
+  if ((rc = wfair_host_finish(c0, c0->d_bd_list, c0->d_bd_lscore, n_reqs, k, flow, n_flows, weight, turns, cost, band, counts, tab, cap, cap_all, load, out_pick,
+                              out_score, out_rank)))
     return mfail(rc);
   return EPPK_OK;
 }

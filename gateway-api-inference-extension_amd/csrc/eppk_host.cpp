@@ -113,6 +113,39 @@ int eppk_hash_prompt(const uint8_t* model, size_t model_len, const uint8_t* prom
   return (int)n;
 }
 
+// SEMANTICS.md §3h: per band, cap the credit of idle flows at `window` cycles behind the flow that is furthest on, then take the cycles
+// every flow has behind it off all of them.  The lift may pass 32 bits on its way (a heavy flow lifted next to a light one near 2^32);
+// what is stored does not: when a flow is lifted the lowest cycle IS the lift, so a lifted flow ends at 0, and every other flow only loses turns.
+int eppk_fair_turns_rebase(uint32_t* turns, const uint16_t* weight, uint32_t n_bands, uint32_t n_flows, uint32_t window) {
+  if (!turns || n_bands < 1u || n_bands > EPPK_MAX_BANDS || n_flows < 1u || n_flows > EPPK_MAX_FLOWS) return EPPK_ERR_ARG;
+  std::vector<uint64_t> t(n_flows);
+  for (uint32_t b = 0; b < n_bands; ++b) {
+    uint32_t* row = turns + (size_t)b * n_flows;
+    uint64_t top = 0;
+    bool any = false;
+    for (uint32_t f = 0; f < n_flows; ++f) {
+      const uint64_t w = weight ? weight[f] : 1u;
+      t[f] = row[f];
+      if (!w) continue;
+      any = true;
+      if (t[f] / w > top) top = t[f] / w;
+    }
+    if (!any) continue;
+    uint64_t low = ~0ull;
+    for (uint32_t f = 0; f < n_flows; ++f) {
+      const uint64_t w = weight ? weight[f] : 1u;
+      if (!w) continue;
+      if (top > window && t[f] / w < top - window) t[f] = (top - window) * w;
+      if (t[f] / w < low) low = t[f] / w;
+    }
+    for (uint32_t f = 0; f < n_flows; ++f) {
+      const uint64_t w = weight ? weight[f] : 1u;
+      if (w) row[f] = (uint32_t)(t[f] - low * w);
+    }
+  }
+  return EPPK_OK;
+}
+
 int eppk_subset_mask(const char* const* addrs, const char* const* ports, uint32_t n_pods, const char* filter, uint64_t* out_mask) {
   if (n_pods && (!addrs || !ports || !out_mask)) return EPPK_ERR_ARG;
   const uint32_t words = (n_pods + 63u) / 64u;

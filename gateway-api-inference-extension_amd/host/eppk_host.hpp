@@ -757,6 +757,12 @@ struct ProfileSpec {
   uint32_t n_flows = 0;                          // bounded: > 0 (at most EPPK_MAX_FLOWS): inside a band the flows take turns, round-robin over
                                                  // Request::flow in flow-id order, where batch order alone decided (SEMANTICS.md §3g;
                                                  // eppk_pick_fair); with or without `bands` and `costed`.  0 = off
+  std::vector<uint16_t> flow_weights;            // with n_flows: a weight >= 1 per flow (size n_flows) -- in every cycle flow f takes up to
+                                                 // flow_weights[f] turns in a row (SEMANTICS.md §3h; eppk_pick_wfair).  Empty = every weight 1
+  uint32_t turn_window = 0;                      // with n_flows: > 0: the scheduler carries the turns every (band, flow) has taken from batch to
+                                                 // batch, so that a flow served in this batch stands behind the others in the next, and
+                                                 // rebases them behind every call (eppk_fair_turns_rebase): a flow that was idle keeps at most
+                                                 // turn_window cycles of credit.  0 = no carry: every batch starts at turn 0
   std::vector<eppk_predicate> predicates;        // metric predicates behind `filter` (SEMANTICS.md §2c): ONE program, evaluated on the device
                                                  // against the gauges of the snapshot; empty = none.  A request they shed gets Unavailable.
 };
@@ -811,6 +817,13 @@ class Scheduler {  // interface.go:55-66
       if (ps.costed && ps.picker != PickerKind::Bounded) return {Code::Internal, std::string("profile ") + ps.name + ": costed needs the bounded picker"};
       if (ps.n_flows && ps.picker != PickerKind::Bounded) return {Code::Internal, std::string("profile ") + ps.name + ": n_flows needs the bounded picker"};
       if (ps.n_flows > EPPK_MAX_FLOWS) return {Code::Internal, std::string("profile ") + ps.name + ": more than " + std::to_string(EPPK_MAX_FLOWS) + " flows"};
+      if ((!ps.flow_weights.empty() || ps.turn_window) && !ps.n_flows)
+        return {Code::Internal, std::string("profile ") + ps.name + ": flow_weights and turn_window need n_flows"};
+      if (!ps.flow_weights.empty() && ps.flow_weights.size() != ps.n_flows)
+        return {Code::Internal, std::string("profile ") + ps.name + ": flow_weights has " + std::to_string(ps.flow_weights.size()) + " entries for " +
+                                    std::to_string(ps.n_flows) + " flows"};
+      for (size_t f = 0; f < ps.flow_weights.size(); ++f)
+        if (!ps.flow_weights[f]) return {Code::Internal, std::string("profile ") + ps.name + ": flow_weights[" + std::to_string(f) + "] is 0"};
       if (ps.bands.size() > EPPK_MAX_BANDS) return {Code::Internal, std::string("profile ") + ps.name + ": more than 8 bands"};
       for (size_t b = 1; b < ps.bands.size(); ++b)
         if (ps.bands[b].reserve < ps.bands[b - 1].reserve)
@@ -826,7 +839,9 @@ class Scheduler {  // interface.go:55-66
         for (size_t s = 0; s < ps.predicates.size() && s < EPPK_MAX_PREDICATES; ++s) prog.stage[s] = ps.predicates[s];
         if (eppk_set_filters(c, &prog, 1) != EPPK_OK) return {Code::Internal, std::string("profile ") + ps.name + ": " + eppk_last_error(c)};
       }
-      profiles_.push_back(Prof{ps, ctx});
+      Prof prof{ps, ctx, {}};
+      if (ps.turn_window) prof.turns.assign((ps.bands.empty() ? 1u : ps.bands.size()) * (size_t)ps.n_flows, 0u);
+      profiles_.push_back(std::move(prof));
       names_.push_back(ps.name);
     }
     return {};
@@ -922,6 +937,7 @@ class Scheduler {  // interface.go:55-66
           const bool costed = p.spec.picker == PickerKind::Bounded && p.spec.costed;
           const bool banded = p.spec.picker == PickerKind::Bounded && !p.spec.bands.empty();
           const bool fair = p.spec.picker == PickerKind::Bounded && p.spec.n_flows != 0u;
+          const bool wfair = fair && (!p.spec.flow_weights.empty() || p.spec.turn_window != 0u);   // weights or carried turns (§3h)
           eppk_band_table table;
           if (fair) {
             flows_.resize(m);
@@ -948,6 +964,11 @@ class Scheduler {  // interface.go:55-66
                              ? eppk_pick_filtered(p.ctx.get(), rows, m, nullptr, nullptr, 1, picks_.data(), scores_.data(), nullptr)
                          : p.spec.picker == PickerKind::BestScore
                              ? eppk_pick_batch(p.ctx.get(), rows, m, nullptr, picks_.data(), scores_.data())
+                         : wfair
+                             ? eppk_pick_wfair(p.ctx.get(), rows, m, fmask, p.spec.k, flows_.data(), p.spec.n_flows,
+                                               p.spec.flow_weights.empty() ? nullptr : p.spec.flow_weights.data(), p.turns.empty() ? nullptr : p.turns.data(),
+                                               costed ? costs_.data() : nullptr, banded ? bands_.data() : nullptr, &table, nullptr, p.spec.cap_all, nullptr,
+                                               picks_.data(), scores_.data(), nullptr)
                          : fair
                              ? eppk_pick_fair(p.ctx.get(), rows, m, fmask, p.spec.k, flows_.data(), p.spec.n_flows, costed ? costs_.data() : nullptr,
                                               banded ? bands_.data() : nullptr, &table, nullptr, p.spec.cap_all, nullptr, picks_.data(), scores_.data(),
@@ -965,6 +986,9 @@ class Scheduler {  // interface.go:55-66
                              ? eppk_pick_weighted_random(p.ctx.get(), rows, m, fmask, 1, seed + lo, picks_.data(), scores_.data())
                              : eppk_pick_random_topk(p.ctx.get(), rows, m, fmask, p.spec.k, seed + lo, picks_.data(), scores_.data());
           if (rc != EPPK_OK) return {Code::Internal, eppk_last_error(p.ctx.get())};
+          if (wfair && !p.turns.empty())                                 // an idle flow keeps at most turn_window cycles of credit; the common part comes off
+            (void)eppk_fair_turns_rebase(p.turns.data(), p.spec.flow_weights.empty() ? nullptr : p.spec.flow_weights.data(), table.n_bands, p.spec.n_flows,
+                                         p.spec.turn_window);
           for (uint32_t i = 0; i < m; ++i) {
             auto& res = results[idx[lo + i]][p.spec.name];     // (present even when empty: the profile has run)
             if (picks_[i] >= 0) res.push_back(ScoredEndpoint{&endpoints_[(size_t)picks_[i]], scores_[i]});
@@ -982,13 +1006,19 @@ class Scheduler {  // interface.go:55-66
     return {};
   }
 
+  // the turns a profile with turn_window carries, [bands][n_flows] (empty: no carry, or no such profile)
+  std::vector<uint32_t> Turns(const std::string& profile) const {
+    for (const Prof& p : profiles_) if (p.spec.name == profile) return p.turns;
+    return {};
+  }
+
   eppk_ctx* context(const std::string& profile) {
     for (Prof& p : profiles_) if (p.spec.name == profile) return p.ctx.get();
     return nullptr;
   }
 
  private:
-  struct Prof { ProfileSpec spec; std::shared_ptr<eppk_ctx> ctx; };
+  struct Prof { ProfileSpec spec; std::shared_ptr<eppk_ctx> ctx; std::vector<uint32_t> turns; };   // turns: [bands][n_flows] with turn_window
   bool Costed(const std::string& profile) const {
     for (const Prof& p : profiles_) if (p.spec.name == profile) return p.spec.costed;
     return false;

@@ -257,6 +257,24 @@ def _flow_words(flow, n_reqs: int):
     return np.ascontiguousarray(a, dtype=np.uint16)
 
 
+def _flow_tables(weight, turns, n_bands: int, n_flows: int):
+    """(weight u16 [n_flows] | None, turns u32 [n_bands][n_flows] | None): the turns as a fresh array the library writes into; a value
+    that does not fit its width is refused here, the library checks the rest."""
+    if weight is not None:
+        a = np.asarray(weight)
+        assert a.shape == (n_flows,), "one weight per flow"
+        if a.size and (a.min() < 0 or a.max() > 0xFFFF):
+            raise EppkError(-1, "weighted fair pick: weight out of range (u16)")
+        weight = np.ascontiguousarray(a, dtype=np.uint16)
+    if turns is not None:
+        a = np.asarray(turns)
+        assert a.shape == (n_bands, n_flows), "turns per band and flow"
+        if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+            raise EppkError(-1, "weighted fair pick: turns out of range (u32)")
+        turns = np.array(a, dtype=np.uint32, copy=True, order="C")
+    return weight, turns
+
+
 class RoundRobinPicker:
     """server.go:84-101 — the reference's picker; the shim's fail-open fallback."""
 
@@ -780,6 +798,70 @@ class BatchedPicker:
                                                        int(cap_all), d_load or None, d_pick, d_score or None, d_rank or None, stream or None),
                     "bounded_resolve_fair_device")
 
+    # -- ... with weights per flow and turns carried between batches (SEMANTICS.md §3h) ------------------
+    def pick_wfair(self, reqs: np.ndarray, k: int, flow, n_flows: int, weight, turns, cost, cap, bands=((_lib.EPPK_BOUNDED_SHED, 0),),
+                   band: Optional[np.ndarray] = None, load: Optional[np.ndarray] = None, mask: Optional[np.ndarray] = None
+                   ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray], Optional[np.ndarray]]:
+        """eppk_pick_wfair: pick_bounded_fair with a weight per flow (u16 [n_flows] >= 1, None: ones) and the turns every (band, flow)
+        took in earlier batches (u32 [n_bands][n_flows], None: zeros and nothing handed back).  Returns what pick_bounded returns, and the
+        turns after this batch (a new array; feed it to the next call, by way of turns_rebase now and then)."""
+        reqs = np.ascontiguousarray(reqs, dtype=np.uint64)
+        assert reqs.ndim == 2 and reqs.shape[1] == self.row_words, "request row stride mismatch"
+        R = reqs.shape[0]
+        mptr = None
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint64)
+            assert mask.shape == (R, (self.n_pods + 63) // 64), "mask shape mismatch"
+            mptr = mask.ctypes.data
+        cap_arr, cap_all, load = _bounded_caps(self.n_pods, cap, load)
+        band = _band_bytes(band, R)
+        flow = _flow_words(flow, R)
+        cost = None if cost is None else _cost_words(cost, R)
+        weight, turns = _flow_tables(weight, turns, len(bands), int(n_flows))
+        picks = np.full(R, -1, dtype=np.int32)
+        scores = np.zeros(R, dtype=np.float64)
+        ranks = np.full(R, _lib.EPPK_RANK_NONE, dtype=np.uint8)
+        self._check(self._lib.eppk_pick_wfair(self._ctx, reqs.ctypes.data, R, mptr, int(k), flow.ctypes.data if flow is not None else None,
+                                              int(n_flows), weight.ctypes.data if weight is not None else None,
+                                              turns.ctypes.data if turns is not None else None, cost.ctypes.data if cost is not None else None,
+                                              band.ctypes.data if band is not None else None, C.byref(_band_table(bands)),
+                                              cap_arr.ctypes.data if cap_arr is not None else None, cap_all,
+                                              load.ctypes.data if load is not None else None, picks.ctypes.data, scores.ctypes.data,
+                                              ranks.ctypes.data), "pick_wfair")
+        return picks, scores, ranks, load, turns
+
+    def pick_wfair_device(self, d_reqs: int, n_reqs: int, d_mask: Optional[int], k: int, d_flow: Optional[int], n_flows: int, d_weight: Optional[int],
+                          d_turns: Optional[int], d_cost: Optional[int], d_band: Optional[int], bands, d_cap: Optional[int], cap_all: int,
+                          d_load: Optional[int], d_pick: int, d_score: Optional[int], d_rank: Optional[int], stream: int = 0) -> None:
+        """eppk_pick_wfair_device: device pointers as ints (d_weight: n_flows u16 or None; d_turns: n_bands x n_flows u32, in / out, or
+        None), asynchronous on `stream`."""
+        self._check(self._lib.eppk_pick_wfair_device(self._ctx, d_reqs, n_reqs, d_mask or None, int(k), d_flow or None, int(n_flows), d_weight or None,
+                                                     d_turns or None, d_cost or None, d_band or None, C.byref(_band_table(bands)), d_cap or None,
+                                                     int(cap_all), d_load or None, d_pick, d_score or None, d_rank or None, stream or None),
+                    "pick_wfair_device")
+
+    def bounded_resolve_wfair_device(self, d_lists: int, d_list_scores: Optional[int], n_reqs: int, k: int, d_flow: Optional[int], n_flows: int,
+                                     d_weight: Optional[int], d_turns: Optional[int], d_cost: Optional[int], cost_flags: int, d_band: Optional[int],
+                                     bands, d_cap: Optional[int], cap_all: int, d_load: Optional[int], d_pick: int, d_score: Optional[int],
+                                     d_rank: Optional[int], stream: int = 0) -> None:
+        """eppk_wfair_resolve_device: the weighted fair resolve alone, over any [n_reqs][k] lists on the device."""
+        self._check(self._lib.eppk_wfair_resolve_device(self._ctx, d_lists, d_list_scores or None, n_reqs, int(k), d_flow or None, int(n_flows),
+                                                        d_weight or None, d_turns or None, d_cost or None, int(cost_flags), d_band or None,
+                                                        C.byref(_band_table(bands)), d_cap or None, int(cap_all), d_load or None, d_pick,
+                                                        d_score or None, d_rank or None, stream or None), "bounded_resolve_wfair_device")
+
+    @staticmethod
+    def turns_rebase(turns, weight, window: int) -> np.ndarray:
+        """eppk_fair_turns_rebase on a copy of `turns` (u32 [n_bands][n_flows]): an idle flow keeps at most `window` cycles of credit, and
+        the cycles every flow has behind it come off all of them.  Host memory only: no context, no device."""
+        turns = np.array(turns, dtype=np.uint32, ndmin=2, copy=True, order="C")
+        weight, _ = _flow_tables(weight, None, turns.shape[0], turns.shape[1])
+        rc = _lib.load_library().eppk_fair_turns_rebase(turns.ctypes.data, weight.ctypes.data if weight is not None else None, turns.shape[0],
+                                                         turns.shape[1], int(window))
+        if rc != 0:
+            raise EppkError(rc, "turns_rebase: bad arguments")
+        return turns
+
     def bounded_geometry(self) -> Tuple[int, int]:
         """(rows per chunk, the largest batch the one-launch kernel takes) of the bounded resolve (EPPK_BOUND_CHUNK)."""
         out = (C.c_uint32 * 2)()
@@ -1119,6 +1201,29 @@ class DeviceGroup:
                                                    load.ctypes.data if load is not None else None, picks.ctypes.data, scores.ctypes.data,
                                                    ranks.ctypes.data), "group_pick_bounded_fair")
         return picks, scores, ranks, load
+
+    def pick_wfair(self, reqs: np.ndarray, k: int, flow, n_flows: int, weight, turns, cost, cap, bands=((_lib.EPPK_BOUNDED_SHED, 0),),
+                   band: Optional[np.ndarray] = None, load: Optional[np.ndarray] = None, mask: Optional[np.ndarray] = None
+                   ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray], Optional[np.ndarray]]:
+        """eppk_group_pick_wfair: BatchedPicker.pick_wfair over the group."""
+        reqs, mask, mptr = self._rows_and_mask(reqs, mask)
+        R = reqs.shape[0]
+        cap_arr, cap_all, load = _bounded_caps(self.n_pods, cap, load)
+        band = _band_bytes(band, R)
+        flow = _flow_words(flow, R)
+        cost = None if cost is None else _cost_words(cost, R)
+        weight, turns = _flow_tables(weight, turns, len(bands), int(n_flows))
+        picks = np.full(R, -1, dtype=np.int32)
+        scores = np.zeros(R, dtype=np.float64)
+        ranks = np.full(R, _lib.EPPK_RANK_NONE, dtype=np.uint8)
+        self._check(self._lib.eppk_group_pick_wfair(self._g, reqs.ctypes.data, R, mptr, int(k), flow.ctypes.data if flow is not None else None,
+                                                    int(n_flows), weight.ctypes.data if weight is not None else None,
+                                                    turns.ctypes.data if turns is not None else None, cost.ctypes.data if cost is not None else None,
+                                                    band.ctypes.data if band is not None else None, C.byref(_band_table(bands)),
+                                                    cap_arr.ctypes.data if cap_arr is not None else None, cap_all,
+                                                    load.ctypes.data if load is not None else None, picks.ctypes.data, scores.ctypes.data,
+                                                    ranks.ctypes.data), "group_pick_wfair")
+        return picks, scores, ranks, load, turns
 
     # -- the pipelined host path over the group (eppk_group_pick_stage_*) ---------------------------------------------
     def stage_buffers(self, which: int, with_mask: bool = False) -> Tuple[np.ndarray, Optional[np.ndarray]]:

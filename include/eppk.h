@@ -731,7 +731,59 @@ int eppk_group_pick_fair(eppk_group* g, const void* reqs, uint32_t n_reqs, const
                          uint32_t n_flows, const uint32_t* cost, const uint8_t* band, const eppk_band_table* bands, const uint32_t* cap,
                          uint32_t cap_all, uint32_t* load, int32_t* out_pick, double* out_score, uint8_t* out_rank);
 
+/* ---- ... with weights per flow and turns carried between batches (SEMANTICS.md §3h) -------------------------------------------------
+ * The fair entry points above give every flow one turn per round and start every batch at flow 0, turn 0: a paid tier and a free tier in
+ * one band take turns one for one, and with one free slot per batch flow 0 gets it in every batch.  Here every flow has a WEIGHT and every
+ * (band, flow) the TURNS it took in earlier batches.  A row is IN THE ORDER iff band < n_bands, flow < n_flows and weight[flow] >= 1; its
+ * turn q is as above; its CYCLE is c = (turns[band][flow] + q) / weight[flow] (floor, in 64 bits).  The fair order of band b is its rows
+ * sorted by (c, flow, q) ascending: in every cycle flow f takes up to weight[f] consecutive turns, the flows in flow-id order, and a flow
+ * that took more turns in the past starts in a later cycle.  Nothing below the order changes (the rounds, the bidder rule, the prefix
+ * sums of cost, the single finish, the rank bytes, EPPK_LAUNCH_BAD_PICK); a row with a bad cost is in the order and holds its turn.
+ *   d_weight      nullable [n_flows] u16; NULL: every weight is 1.  A weight belongs to the flow id: the same in every band.  A weight of
+ *                 0 takes the flow's rows OUT of the order: they are answered exactly like a flow >= n_flows (the *_device forms: effective
+ *                 band 0xFF, EPPK_NO_PICK / 0.0 / EPPK_RANK_NONE, EPPK_LAUNCH_BAD_REQUEST_ROW, the list still checked; the host-buffer
+ *                 forms refuse the batch with EPPK_ERR_ARG and name the lowest such row, and refuse any zero weight, naming the flow).
+ *   d_turns       nullable [n_bands][n_flows] u32, in / out; NULL: zeros, and nothing is reported (as d_load).  Behind the finish
+ *                 turns[b][f] := min(2^32 - 1, turns[b][f] + taken[b][f]), taken = the rows of (b, f) in the order whose out_pick is not
+ *                 EPPK_NO_PICK: a placed row and a spilled row count, a shed row and a row without a valid entry do not -- a flow whose
+ *                 requests were shed keeps its place at the front of the next batch.
+ *   every other argument as for the fair entry points.
+ * The result, d_turns included, is a pure function of the arguments.  d_weight NULL and d_turns NULL is eppk_fair_resolve_device bit for
+ * bit; ones and zeros equal NULL / NULL; adding m * weight[f] to every turns[b][f] of a band (without saturation) changes no pick, rank,
+ * score or load and adds the same to the turns handed back.  The *_device forms never wait for the host: d_weight and d_turns are read on
+ * the device (once, into the context's own memory) and d_turns is written by the last launch on `stream`.  The notes of the fair forms
+ * hold (one stream at a time per context; the scratch grows on demand: that of the fair forms and 100 KiB more); one launch more in
+ * front (the copy) and with a d_turns two behind.  Not here: turns in cost units (a turn is a request whatever it costs); a tie-break by
+ * arrival instead of flow id; assumed load (EPPK_ERR_ARG while it is on, as above).  Errors: as for the fair forms. */
+int eppk_wfair_resolve_device(eppk_ctx* ctx, const int32_t* d_lists, const double* d_list_scores, uint32_t n_reqs, uint32_t k,
+                              const uint16_t* d_flow, uint32_t n_flows, const uint16_t* d_weight, uint32_t* d_turns,
+                              const uint32_t* d_cost, uint32_t cost_flags, const uint8_t* d_band, const eppk_band_table* bands,
+                              const uint32_t* d_cap, uint32_t cap_all, uint32_t* d_load, int32_t* d_out_pick, double* d_out_score,
+                              uint8_t* d_out_rank, void* stream);
+int eppk_pick_wfair_device(eppk_ctx* ctx, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, uint32_t k,
+                           const uint16_t* d_flow, uint32_t n_flows, const uint16_t* d_weight, uint32_t* d_turns, const uint32_t* d_cost,
+                           const uint8_t* d_band, const eppk_band_table* bands, const uint32_t* d_cap, uint32_t cap_all, uint32_t* d_load,
+                           int32_t* d_out_pick, double* d_out_score, uint8_t* d_out_rank, void* stream);
+/* Host buffers: weight u16 [n_flows] or NULL, turns u32 [n_bands][n_flows] in / out or NULL. */
+int eppk_pick_wfair(eppk_ctx* ctx, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint16_t* flow,
+                    uint32_t n_flows, const uint16_t* weight, uint32_t* turns, const uint32_t* cost, const uint8_t* band,
+                    const eppk_band_table* bands, const uint32_t* cap, uint32_t cap_all, uint32_t* load, int32_t* out_pick,
+                    double* out_score, uint8_t* out_rank);
+/* Over a group, as eppk_group_pick_fair: member 0 resolves; equals eppk_pick_wfair on the unsharded batch bit for bit. */
+int eppk_group_pick_wfair(eppk_group* g, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint16_t* flow,
+                          uint32_t n_flows, const uint16_t* weight, uint32_t* turns, const uint32_t* cost, const uint8_t* band,
+                          const eppk_band_table* bands, const uint32_t* cap, uint32_t cap_all, uint32_t* load, int32_t* out_pick,
+                          double* out_score, uint8_t* out_rank);
+
 /* ---- adjacent host-side steps of the same path ---------------------------------------------- */
+
+/* Carried turns (eppk_pick_wfair) only ever grow, and a flow that was idle for an hour comes back with an hour of credit.  A pure host
+ * function on host memory (no context, no device).  Per band, over the flows with weight >= 1 (weight NULL: every weight 1), with
+ * cyc[f] = turns[f] / w[f] and M = max cyc: (1) if M > window, every flow with cyc[f] < M - window is lifted to (M - window) * w[f] -- an
+ * idle flow keeps at most `window` cycles of credit; (2) with m = min cyc after the lift, every flow loses m * w[f], which changes no
+ * order (the rebase equality above).  64-bit arithmetic; every result fits 32 bits.  Flows of weight 0 are left alone.  EPPK_ERR_ARG for
+ * a null turns, n_bands outside 1 .. EPPK_MAX_BANDS and n_flows outside 1 .. EPPK_MAX_FLOWS. */
+int eppk_fair_turns_rebase(uint32_t* turns, const uint16_t* weight, uint32_t n_bands, uint32_t n_flows, uint32_t window);
 
 /* Chain-hash a prompt into block hashes (0602-…/README.md:99): XXH64, seed 0,
  * h[-1] = XXH64(model), h[i] = XXH64(prompt[i*block_chars .. (i+1)*block_chars) || LE64(h[i-1])).
