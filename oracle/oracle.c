@@ -237,43 +237,47 @@ uint32_t orc_index_advance_epoch(orc_index* ix) {
 }
 
 /* SEMANTICS.md 6c.  age(h) = min(63, epoch - stamp(h)); cutage(p) = the smallest b >= 1 with #{h containing p : age(h) <= b} > cap;
- * p leaves every hash of age >= cutage(p).  (Naive: one pass per pod.) */
+ * p leaves every hash of age >= cutage(p).  The pods are trimmed independently of one another -- a hash's age does not change and its
+ * pod set holds a pod once -- so the table is walked twice for all of them, not twice per pod: the table keeps the entries of every hash
+ * it ever held, and a soak of fresh hashes (tests/test_gpu_churn.py) made one pass per pod the whole of its run time. */
 uint64_t orc_index_trim_pods(orc_index* ix, uint32_t n_pods_max, uint32_t cap) {
   uint64_t removed = 0;
+  if (n_pods_max == 0) return 0;
+  uint64_t* hist = (uint64_t*)calloc((size_t)n_pods_max * 64u, sizeof(uint64_t));
+  int* cut = (int*)malloc((size_t)n_pods_max * sizeof(int));
+  if (!hist || !cut) { free(hist); free(cut); return 0; }
+  for (uint64_t i = 0; i < ix->cap; ++i) {
+    const orc_entry* e = &ix->tab[i];
+    if (!e->used || e->n == 0) continue;
+    uint32_t age = ix->epoch - e->stamp;
+    if (age > 63u) age = 63u;
+    for (uint32_t j = 0; j < e->n; ++j)
+      if (e->pods[j] < n_pods_max) hist[(size_t)e->pods[j] * 64u + age]++;
+  }
+  int any = 0;
   for (uint32_t p = 0; p < n_pods_max; ++p) {
-    uint64_t hist[64];
-    memset(hist, 0, sizeof hist);
-    for (uint64_t i = 0; i < ix->cap; ++i) {
-      const orc_entry* e = &ix->tab[i];
-      if (!e->used || e->n == 0) continue;
-      for (uint32_t j = 0; j < e->n; ++j)
-        if (e->pods[j] == p) {
-          uint32_t age = ix->epoch - e->stamp;
-          hist[age < 63u ? age : 63u]++;
-        }
-    }
     uint64_t cum = 0;
-    int cut = -1;
+    cut[p] = -1;
     for (int b = 0; b < 64; ++b) {
-      cum += hist[b];
-      if (cum > cap) { cut = b < 1 ? 1 : b; break; }
-    }
-    if (cut < 0) continue;
-    for (uint64_t i = 0; i < ix->cap; ++i) {
-      orc_entry* e = &ix->tab[i];
-      if (!e->used || e->n == 0) continue;
-      uint32_t age = ix->epoch - e->stamp;
-      if (age > 63u) age = 63u;
-      if ((int)age < cut) continue;
-      for (uint32_t j = 0; j < e->n; ++j)
-        if (e->pods[j] == p) {
-          memmove(e->pods + j, e->pods + j + 1, (e->n - j - 1) * sizeof(uint32_t));
-          e->n--;
-          removed++;
-          break;
-        }
+      cum += hist[(size_t)p * 64u + (size_t)b];
+      if (cum > cap) { cut[p] = b < 1 ? 1 : b; any = 1; break; }
     }
   }
+  for (uint64_t i = 0; any && i < ix->cap; ++i) {
+    orc_entry* e = &ix->tab[i];
+    if (!e->used || e->n == 0) continue;
+    uint32_t age = ix->epoch - e->stamp;
+    if (age > 63u) age = 63u;
+    uint32_t keep = 0;
+    for (uint32_t j = 0; j < e->n; ++j) {
+      const uint32_t p = e->pods[j];
+      if (p < n_pods_max && cut[p] >= 0 && (int)age >= cut[p]) { removed++; continue; }
+      e->pods[keep++] = p;
+    }
+    e->n = keep;
+  }
+  free(hist);
+  free(cut);
   return removed;
 }
 

@@ -40,8 +40,6 @@ def test_pipelined_stage_sets_against_the_oracle(pkg, orc, monkeypatch, eppk_mod
     chained on the device behind each pick and batch k + 1 must already see what batch k taught the index (the oracle inserts between
     batches), although its rows were uploaded before that update finished."""
     if zc_max is not None:
-        if eppk_mode != "default" and not (R == 1500 or (R == 3000 and learn)):
-            pytest.skip("outside the default library mode the zero-copy switch is varied for the two cheapest LEARN cases only (GPU time)")
         monkeypatch.setenv("EPPK_ZERO_COPY_MAX", zc_max)
     wl = pkg.workload.make_workload(5, R=R, P=4096, n_groups=16, masked=masked)
     batches = [wl.reqs] + [pkg.workload.make_requests(wl, 31 + i) for i in range(3)]
@@ -96,8 +94,6 @@ def test_zero_copy_small_batches(pkg, orc, monkeypatch, eppk_mode, zc_max, R, ma
     if zc_max is None:
         monkeypatch.delenv("EPPK_ZERO_COPY_MAX", raising=False)           # the library's default (3072)
     else:
-        if eppk_mode != "default" and R > 37:
-            pytest.skip("outside the default library mode the zero-copy switch is varied for the two cheapest sizes only (GPU time)")
         monkeypatch.setenv("EPPK_ZERO_COPY_MAX", zc_max)
     wl = pkg.workload.make_workload(5, R=R, P=4096, n_groups=16, masked=masked)
     J = (wl.P + 63) // 64
