@@ -19,6 +19,7 @@ EPPK_MAX_BANDS = 8
 EPPK_MAX_COST = 0x00FFFFFF
 EPPK_COST_PER_ENTRY = 1
 EPPK_MAX_FLOWS = 1024
+EPPK_SFAIR_MAX_REQS = 131072
 
 STATUS = {0: "EPPK_OK", -1: "EPPK_ERR_ARG", -2: "EPPK_ERR_LIMIT", -3: "EPPK_ERR_DEVICE",
           -4: "EPPK_ERR_NO_SNAPSHOT", -5: "EPPK_ERR_INDEX_FULL", -6: "EPPK_ERR_NOMEM"}
@@ -42,6 +43,7 @@ SYMBOLS = [
     "eppk_costed_resolve_device", "eppk_pick_costed_device", "eppk_pick_costed", "eppk_group_pick_costed",
     "eppk_fair_resolve_device", "eppk_pick_fair_device", "eppk_pick_fair", "eppk_group_pick_fair",
     "eppk_wfair_resolve_device", "eppk_pick_wfair_device", "eppk_pick_wfair", "eppk_group_pick_wfair", "eppk_fair_turns_rebase",
+    "eppk_sfair_resolve_device", "eppk_pick_sfair_device", "eppk_pick_sfair", "eppk_group_pick_sfair",
     "eppk_group_create", "eppk_group_destroy", "eppk_group_last_error", "eppk_group_size", "eppk_group_ctx", "eppk_group_ranks_seen",
     "eppk_group_set_min_shard", "eppk_group_snapshot_publish", "eppk_group_index_clear", "eppk_group_index_insert",
     "eppk_group_index_remove_pod", "eppk_group_index_advance_epoch", "eppk_group_index_evict_older", "eppk_group_pick_batch",
@@ -183,6 +185,10 @@ def load_library() -> C.CDLL:
     lib.eppk_pick_wfair_device.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp, vp]
     lib.eppk_pick_wfair.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp]
     lib.eppk_group_pick_wfair.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp]
+    lib.eppk_sfair_resolve_device.argtypes = lib.eppk_wfair_resolve_device.argtypes
+    lib.eppk_pick_sfair_device.argtypes = lib.eppk_pick_wfair_device.argtypes
+    lib.eppk_pick_sfair.argtypes = lib.eppk_pick_wfair.argtypes
+    lib.eppk_group_pick_sfair.argtypes = lib.eppk_group_pick_wfair.argtypes
     lib.eppk_fair_turns_rebase.argtypes = [vp, vp, u32, u32, u32]
     lib.eppk_group_create.argtypes = [C.POINTER(Cfg), C.POINTER(i32), u32, u32, C.POINTER(vp)]
     lib.eppk_group_destroy.argtypes = [vp]

@@ -14,6 +14,7 @@
 #include "eppk_costed.hip.h"
 #include "eppk_fair.hip.h"
 #include "eppk_wfair.hip.h"
+#include "eppk_sfair.hip.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -234,6 +235,13 @@ struct eppk_ctx {
   DBuf<uint16_t> d_fr_flow;                                 // flow ids of the host forms
   // ... with weights per flow and turns carried between batches (SEMANTICS.md §3h; eppk_wfair.hip.h): the fair picker's buffers, and
   DBuf<uint32_t> d_wf;                                      // kWfairWords words: t[G] | taken[G] | w[n_flows] of the call, then the host forms' turns and weights
+  // ... in cost units, the rows sorted by carried service (SEMANTICS.md §3i; eppk_sfair.hip.h): the fair picker's buffers, and
+  DBuf<uint64_t> d_sf;                                      // kSfairWords words: base[8] | taken[G], then 32-bit s[G] | w[n_flows], the host forms' service and weights
+  DBuf<uint64_t> d_sf_ch;                                   // [n_chunks][G]: the charges of every key per chunk, then in the chunks in front
+  DBuf<uint64_t> d_sf_tag;                                  // the start tag per request
+  DBuf<uint32_t> d_sf_charge;                               // the charge per request (its cost, or 0 for a bad cost)
+  DBuf<uint32_t> d_sf_perm;                                 // the second permutation of the sort's ping-pong (the first is d_bn_perm)
+  DBuf<uint32_t> d_sf_dh;                                   // total[2048], then [n_chunks][2048]: the digit histogram of a pass
 
   // measurement
   bool prof = false;
@@ -3796,6 +3804,240 @@ int eppk_pick_wfair(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint64
                            out_rank);
 }
 
+// ---- ... in cost units: the rows sorted by carried service (SEMANTICS.md §3i; eppk_sfair.hip.h) ------------------------------------------
+
+namespace {
+
+// The arguments every sfair entry point shares: those of the wfair forms; costs per request only (the order needs one cost per row
+// before any list is read); at most EPPK_SFAIR_MAX_REQS rows, so that the sort key needs no clamp.
+int sfair_check(eppk_ctx* c, const char* who, uint32_t n_reqs, uint32_t k, const eppk_band_table* t, uint32_t n_flows, const void* cost, uint32_t cost_flags,
+                eppk::BandTab* tab) {
+  const int rc = wfair_check(c, who, k, t, n_flows, cost, cost_flags, tab);
+  if (rc) return rc;
+  if (cost_flags) return fail(c, EPPK_ERR_ARG, std::string(who) + ": cost flags " + std::to_string(cost_flags) + " (costs per entry have no order in cost units)");
+  if (n_reqs > EPPK_SFAIR_MAX_REQS) return fail(c, EPPK_ERR_LIMIT, std::string(who) + ": n_reqs > " + std::to_string(EPPK_SFAIR_MAX_REQS));
+  return EPPK_OK;
+}
+
+// A row the host forms refuse is a row wfair_host_counts refuses: band, flow, weight 0, cost.
+int sfair_host_counts(eppk_ctx* c, const char* who, const uint8_t* band, const uint16_t* flow, uint32_t n_flows, const uint16_t* weight, const uint32_t* cost,
+                      uint32_t n_reqs, uint32_t n_bands, uint32_t counts[EPPK_MAX_BANDS]) {
+  return wfair_host_counts(c, who, band, flow, n_flows, weight, cost, n_reqs, n_bands, counts);
+}
+
+int sfair_scratch(eppk_ctx* c) { return ctx_grow(c, (size_t)eppk::kSfairWords, {{c->d_sf, sizeof(uint64_t), "service fair picker: service and weights"}}); }
+
+// The launches of the service fair resolve on `st` (arguments checked by the caller; n_reqs != 0).  In front the order: sfair_stage_kernel,
+// sfair_hist_kernel, fair_offsets_kernel (seg[]), sfair_offsets_kernel over the charges, sfair_tag_kernel, then five passes of
+// sfair_digit_kernel / sfair_offsets_kernel / sfair_sort_kernel between perm and a second buffer, the last pass into perm.  Behind it
+// wfair_resolve's round loop and finish (COPIED from there, not called: wfair_resolve is one function, and taking the loop out of it
+// would change what the wfair entry points execute), and with a d_service the carry (sfair_taken_kernel, sfair_carry_kernel: d_service
+// is written by the last launch on `st`).
+int sfair_resolve(eppk_ctx* c, const int32_t* d_lists, const double* d_scores, uint32_t n_reqs, uint32_t k, const uint16_t* d_flow, uint32_t n_flows,
+                  const uint16_t* d_weight, uint32_t* d_service, const uint32_t* d_cost, const uint8_t* d_band, const eppk::BandTab& tab, const uint32_t* counts,
+                  const uint32_t* d_cap, uint32_t cap_all, uint32_t* d_load, int32_t* d_out_pick, double* d_out_score, uint8_t* d_out_rank, hipStream_t st) {
+  const uint32_t P = c->n_pods, chunk = c->bound_chunk;
+  const eppk::CostOf cost{d_cost, k, 0u};
+  const size_t G = (size_t)tab.n_bands * n_flows;
+  int rc;
+  uint8_t* state = d_out_rank;
+  if (!state) {
+    if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_bd_state, 1u, "bounded picker: request states"}}))) return rc;
+    state = c->d_bd_state;
+  }
+  const uint32_t n_chunks = (uint32_t)(((uint64_t)n_reqs + chunk - 1u) / chunk);
+  if ((rc = bounded_pod_scratch(c))) return rc;
+  if ((rc = ctx_grow(c, (size_t)n_chunks * P, {{c->d_bd_hist, sizeof(uint32_t), "bounded picker: bid histogram"}}))) return rc;
+  if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_bn_perm, sizeof(uint32_t), "banded picker: band order"}}))) return rc;
+  if ((rc = ctx_grow(c, eppk::kBandSegWords + (size_t)n_chunks * EPPK_MAX_BANDS, {{c->d_bn_bh, sizeof(uint32_t), "banded picker: band histogram"}}))) return rc;
+  if ((rc = ctx_grow(c, (size_t)EPPK_MAX_PODS, {{c->d_cs_acc, sizeof(uint32_t), "costed picker: takers' totals"}}))) return rc;
+  if ((rc = ctx_grow(c, G + (size_t)n_chunks * G, {{c->d_fr_fh, sizeof(uint32_t), "fair picker: flow histogram"}}))) return rc;
+  if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_fr_key, sizeof(uint16_t), "fair picker: keys"}, {c->d_fr_band, 1u, "fair picker: effective bands"}}))) return rc;
+  if ((rc = sfair_scratch(c))) return rc;
+  if ((rc = ctx_grow(c, (size_t)n_chunks * G, {{c->d_sf_ch, sizeof(uint64_t), "service fair picker: charge histogram"}}))) return rc;
+  if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_sf_tag, sizeof(uint64_t), "service fair picker: tags"}, {c->d_sf_charge, sizeof(uint32_t), "service fair picker: charges"},
+                                                  {c->d_sf_perm, sizeof(uint32_t), "service fair picker: second permutation"}}))) return rc;
+  if ((rc = ctx_grow(c, (size_t)eppk::kSfairDigits * (n_chunks + 1u), {{c->d_sf_dh, sizeof(uint32_t), "service fair picker: digit histogram"}}))) return rc;
+  // dynamic LDS above the default limit: raised once, to the largest request the kernel can make (occupancy_of, g_lds_limit)
+  const size_t hist_lds = eppk::sfair_hist_lds(G), tag_lds = eppk::sfair_tag_lds(G, n_flows), taken_lds = eppk::sfair_taken_lds(G);
+  int per_cu = 0;
+  if (hist_lds > 64u * 1024u && (rc = occupancy_of(c, (const void*)eppk::sfair_hist_kernel, eppk::kBoundThreads, eppk::kSfairHistMaxLds, &per_cu))) return rc;
+  if (tag_lds > 64u * 1024u && (rc = occupancy_of(c, (const void*)eppk::sfair_tag_kernel, 64u, eppk::kSfairTagMaxLds, &per_cu))) return rc;
+  uint32_t* seg = c->d_bn_bh;
+  uint32_t* cnt = c->d_fr_fh;
+  uint32_t* fh = c->d_fr_fh + G;
+  uint32_t* perm = c->d_bn_perm;
+  uint32_t* room = c->d_bd_pods;
+  uint32_t* acc = c->d_cs_acc;
+  uint64_t* base = c->d_sf + eppk::kSfairBase;
+  uint64_t* taken = c->d_sf + eppk::kSfairTaken;
+  uint32_t* s_own = (uint32_t*)c->d_sf.get() + eppk::kSfairS;
+  uint32_t* w_own = (uint32_t*)c->d_sf.get() + eppk::kSfairW;
+  uint32_t* dtotal = c->d_sf_dh;
+  uint32_t* dh = c->d_sf_dh + eppk::kSfairDigits;
+  const uint16_t* key = c->d_fr_key;
+  const uint8_t* eband = c->d_fr_band;
+  uint32_t* load = d_load;
+  if (!load) {
+    load = c->d_bd_pods + EPPK_MAX_PODS;
+    HIPCHK(c, hipMemsetAsync(load, 0, (size_t)EPPK_MAX_PODS * sizeof(uint32_t), st));
+  }
+  if (d_cost) HIPCHK(c, hipMemsetAsync(acc, 0, (size_t)EPPK_MAX_PODS * sizeof(uint32_t), st));
+  HIPCHK(c, hipMemsetAsync(seg, 0, (size_t)eppk::kBandSegWords * sizeof(uint32_t), st));
+  HIPCHK(c, hipMemsetAsync(state, (int)eppk::kBoundUnassigned, n_reqs, st));
+  // grid-stride loops as wide as the CUs this context may use (EPPK_MAX_CU): the results do not depend on the width
+  const uint32_t wide = (uint32_t)c->num_cu * 4u;
+  const uint32_t chunk_grid = n_chunks < wide ? n_chunks : wide;
+  const uint32_t pod_wgs = (P + eppk::kBoundScanPods - 1u) / eppk::kBoundScanPods, pod_grid = pod_wgs < wide ? pod_wgs : wide;
+  const uint32_t key_wgs = (uint32_t)((G + eppk::kBoundScanPods - 1u) / eppk::kBoundScanPods), key_grid = key_wgs < wide ? key_wgs : wide;
+  const uint32_t row_wgs = (uint32_t)(((uint64_t)n_reqs + eppk::kBoundThreads - 1u) / eppk::kBoundThreads), row_grid = row_wgs < wide * 2u ? row_wgs : wide * 2u;
+  const uint32_t gk_wgs = (uint32_t)((G + eppk::kBoundThreads - 1u) / eppk::kBoundThreads), gk_grid = gk_wgs < wide ? gk_wgs : wide;
+  const uint32_t digit_wgs = eppk::kSfairDigits / eppk::kBoundScanPods, digit_grid = digit_wgs < wide ? digit_wgs : wide;
+  const dim3 scan_threads(eppk::kBoundScanSegs * eppk::kBoundScanPods);
+  hipLaunchKernelGGL(eppk::sfair_stage_kernel, dim3(gk_grid), dim3(eppk::kBoundThreads), 0, st, d_weight, (const uint32_t*)d_service, tab.n_bands, n_flows, w_own, s_own,
+                     taken, base);
+  hipLaunchKernelGGL(eppk::sfair_hist_kernel, dim3(chunk_grid), dim3(eppk::kBoundThreads), hist_lds, st, d_band, d_flow, d_cost, (const uint32_t*)w_own, n_reqs,
+                     tab.n_bands, n_flows, chunk, n_chunks, fh, (uint64_t*)c->d_sf_ch, (uint16_t*)c->d_fr_key, (uint8_t*)c->d_fr_band, (uint32_t*)c->d_sf_charge);
+  hipLaunchKernelGGL(eppk::fair_offsets_kernel, dim3(key_grid), scan_threads, 0, st, fh, n_chunks, tab.n_bands, n_flows, cnt, seg);
+  hipLaunchKernelGGL(eppk::sfair_offsets_kernel<uint64_t>, dim3(key_grid), scan_threads, 0, st, (uint64_t*)c->d_sf_ch, n_chunks, (uint32_t)G, (uint64_t*)nullptr);
+  hipLaunchKernelGGL(eppk::sfair_tag_kernel, dim3(chunk_grid), dim3(64), tag_lds, st, key, (const uint32_t*)c->d_sf_charge, n_reqs, tab.n_bands, n_flows, chunk,
+                     n_chunks, (const uint64_t*)c->d_sf_ch, (const uint32_t*)s_own, (const uint32_t*)w_own, (uint64_t*)c->d_sf_tag, base);
+  for (uint32_t pass = 0; pass < eppk::kSfairPasses; ++pass) {        // perm <- identity, second <- perm, ..., perm <- second: five passes end in perm
+    const uint32_t* src = pass == 0u ? nullptr : (pass & 1u) ? perm : (uint32_t*)c->d_sf_perm;
+    uint32_t* dst = (pass & 1u) ? (uint32_t*)c->d_sf_perm : perm;
+    hipLaunchKernelGGL(eppk::sfair_digit_kernel, dim3(chunk_grid), dim3(eppk::kBoundThreads), 0, st, src, pass, key, eband, (const uint64_t*)c->d_sf_tag,
+                       (const uint64_t*)base, n_reqs, tab.n_bands, n_flows, chunk, n_chunks, dh);
+    hipLaunchKernelGGL(eppk::sfair_offsets_kernel<uint32_t>, dim3(digit_grid), scan_threads, 0, st, dh, n_chunks, eppk::kSfairDigits, dtotal);
+    hipLaunchKernelGGL(eppk::sfair_sort_kernel, dim3(chunk_grid), dim3(64), 0, st, src, pass, key, eband, (const uint64_t*)c->d_sf_tag, (const uint64_t*)base, n_reqs,
+                       tab.n_bands, n_flows, chunk, n_chunks, (const uint32_t*)dh, (const uint32_t*)dtotal, dst);
+  }
+  if (P) for (uint32_t b = 0; b < tab.n_bands; ++b) {
+    uint32_t band_grid = chunk_grid;
+    if (counts) {
+      if (!counts[b]) continue;
+      const uint32_t band_chunks = (uint32_t)(((uint64_t)counts[b] + chunk - 1u) / chunk);
+      band_grid = band_chunks < wide ? band_chunks : wide;
+    }
+    const eppk::CostRoomGlobal room_now{d_cap, cap_all, tab.reserve[b], load, acc};
+    for (uint32_t j = 0; j < k; ++j) {
+      if (d_cost) {
+        hipLaunchKernelGGL(eppk::costed_count_kernel, dim3(band_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, k, j, P, chunk, (const uint32_t*)seg, b,
+                           (const uint32_t*)perm, cost, room_now, state, c->d_bd_hist);
+        hipLaunchKernelGGL(eppk::costed_scan_kernel, dim3(pod_grid), scan_threads, 0, st, c->d_bd_hist, chunk, (const uint32_t*)seg, b, P, d_cap, cap_all,
+                           tab.reserve[b], load, acc, room);
+        hipLaunchKernelGGL(eppk::costed_assign_kernel, dim3(band_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, d_scores, k, j, P, chunk, (const uint32_t*)seg,
+                           b, (const uint32_t*)perm, cost, (const uint32_t*)c->d_bd_hist, (const uint32_t*)room, acc, state, d_out_pick, d_out_score);
+      } else {
+        hipLaunchKernelGGL(eppk::banded_count_kernel, dim3(band_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, k, j, P, chunk, (const uint32_t*)seg, b,
+                           (const uint32_t*)perm, (const uint8_t*)state, c->d_bd_hist);
+        hipLaunchKernelGGL(eppk::banded_scan_kernel, dim3(pod_grid), scan_threads, 0, st, c->d_bd_hist, chunk, (const uint32_t*)seg, b, P, d_cap, cap_all,
+                           tab.reserve[b], load, room);
+        hipLaunchKernelGGL(eppk::banded_assign_kernel, dim3(band_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, d_scores, k, j, P, chunk, (const uint32_t*)seg,
+                           b, (const uint32_t*)perm, (const uint32_t*)c->d_bd_hist, (const uint32_t*)room, state, d_out_pick, d_out_score);
+      }
+    }
+  }
+  if (d_cost)
+    hipLaunchKernelGGL(eppk::costed_finish_kernel, dim3(row_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, d_scores, n_reqs, k, P, cost, eband, tab.n_bands,
+                       tab.spill, load, (const uint32_t*)acc, state, d_out_pick, d_out_score, c->d_status);
+  else
+    hipLaunchKernelGGL(eppk::banded_finish_kernel, dim3(row_grid), dim3(eppk::kBoundThreads), 0, st, d_lists, d_scores, n_reqs, k, P, eband, tab.n_bands, tab.spill,
+                       load, state, d_out_pick, d_out_score, c->d_status);
+  if (d_service) {
+    hipLaunchKernelGGL(eppk::sfair_taken_kernel, dim3(chunk_grid), dim3(eppk::kBoundThreads), taken_lds, st, key, (const uint32_t*)c->d_sf_charge,
+                       (const int32_t*)d_out_pick, n_reqs, tab.n_bands, n_flows, chunk, n_chunks, taken);
+    hipLaunchKernelGGL(eppk::sfair_carry_kernel, dim3(gk_grid), dim3(eppk::kBoundThreads), 0, st, (const uint32_t*)s_own, (const uint64_t*)taken, tab.n_bands, n_flows,
+                       d_service);
+  }
+  HIPCHK(c, hipGetLastError());
+  return EPPK_OK;
+}
+
+// As wfair_host_finish, with the service table where the turns are.
+int sfair_host_finish(eppk_ctx* c, const int32_t* d_lists, const double* d_scores, uint32_t n_reqs, uint32_t k, const uint16_t* flow, uint32_t n_flows,
+                      const uint16_t* weight, uint32_t* service, const uint32_t* cost, const uint8_t* band, const uint32_t* counts, const eppk::BandTab& tab,
+                      const uint32_t* cap, uint32_t cap_all, uint32_t* load, int32_t* out_pick, double* out_score, uint8_t* out_rank) {
+  int rc;
+  if (band) {
+    if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_bn_band, 1u, "banded picker: bands"}}))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_bn_band, band, n_reqs, hipMemcpyHostToDevice, c->stream));
+  }
+  if (flow) {
+    if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_fr_flow, sizeof(uint16_t), "fair picker: flows"}}))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_fr_flow, flow, (size_t)n_reqs * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+  }
+  if (cost) {
+    if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_cs_cost, sizeof(uint32_t), "costed picker: costs"}}))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_cs_cost, cost, (size_t)n_reqs * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  }
+  if ((rc = sfair_scratch(c))) return rc;
+  const size_t G = (size_t)tab.n_bands * n_flows;
+  uint32_t* d_service = service ? (uint32_t*)c->d_sf.get() + eppk::kSfairHostS : nullptr;
+  uint16_t* d_weight = weight ? (uint16_t*)((uint32_t*)c->d_sf.get() + eppk::kSfairHostW) : nullptr;
+  if (service) HIPCHK(c, hipMemcpyAsync(d_service, service, G * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  if (weight) HIPCHK(c, hipMemcpyAsync(d_weight, weight, (size_t)n_flows * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+  return bounded_host_around(c, n_reqs, cap, load, out_pick, out_score, out_rank,
+                             [&](const uint32_t* d_cap, uint32_t* d_load, int32_t* d_pick, double* d_score, uint8_t* d_rank) {
+                               const int rcr = sfair_resolve(c, d_lists, d_scores, n_reqs, k, flow ? (const uint16_t*)c->d_fr_flow : nullptr, n_flows, d_weight,
+                                                             d_service, cost ? (const uint32_t*)c->d_cs_cost : nullptr,
+                                                             band ? (const uint8_t*)c->d_bn_band : nullptr, tab, counts, d_cap, cap_all, d_load, d_pick, d_score,
+                                                             d_rank, c->stream);
+                               if (rcr) return rcr;
+                               if (service) HIPCHK(c, hipMemcpyAsync(service, d_service, G * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+                               return (int)EPPK_OK;
+                             });
+}
+
+}  // namespace
+
+int eppk_sfair_resolve_device(eppk_ctx* c, const int32_t* d_lists, const double* d_list_scores, uint32_t n_reqs, uint32_t k, const uint16_t* d_flow,
+                              uint32_t n_flows, const uint16_t* d_weight, uint32_t* d_service, const uint32_t* d_cost, uint32_t cost_flags, const uint8_t* d_band,
+                              const eppk_band_table* bands, const uint32_t* d_cap, uint32_t cap_all, uint32_t* d_load, int32_t* d_out_pick, double* d_out_score,
+                              uint8_t* d_out_rank, void* stream) {
+  if (!c || ((!d_lists || !d_out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_sfair_resolve_device: null argument");
+  eppk::BandTab tab;
+  const int rcc = sfair_check(c, "eppk_sfair_resolve_device", n_reqs, k, bands, n_flows, d_cost, cost_flags, &tab);
+  if (rcc) return rcc;
+  if (n_reqs == 0) return EPPK_OK;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  return sfair_resolve(c, d_lists, d_list_scores, n_reqs, k, d_flow, n_flows, d_weight, d_service, d_cost, d_band, tab, nullptr, d_cap, cap_all, d_load, d_out_pick,
+                       d_out_score, d_out_rank, stream ? (hipStream_t)stream : c->stream);
+}
+
+int eppk_pick_sfair_device(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, uint32_t k, const uint16_t* d_flow, uint32_t n_flows,
+                           const uint16_t* d_weight, uint32_t* d_service, const uint32_t* d_cost, const uint8_t* d_band, const eppk_band_table* bands,
+                           const uint32_t* d_cap, uint32_t cap_all, uint32_t* d_load, int32_t* d_out_pick, double* d_out_score, uint8_t* d_out_rank,
+                           void* stream) {
+  if (!c || ((!d_reqs || !d_out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_sfair_device: null argument");
+  eppk::BandTab tab;
+  int rc = sfair_check(c, "eppk_pick_sfair_device", n_reqs, k, bands, n_flows, d_cost, 0u, &tab);
+  if (rc) return rc;
+  if (n_reqs == 0) return EPPK_OK;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if ((rc = bounded_lists(c, n_reqs))) return rc;
+  if ((rc = eppk_pick_topk_device(c, d_reqs, n_reqs, d_cand_mask, k, c->d_bd_list, c->d_bd_lscore, stream))) return rc;
+  return sfair_resolve(c, c->d_bd_list, c->d_bd_lscore, n_reqs, k, d_flow, n_flows, d_weight, d_service, d_cost, d_band, tab, nullptr, d_cap, cap_all, d_load,
+                       d_out_pick, d_out_score, d_out_rank, stream ? (hipStream_t)stream : c->stream);
+}
+
+int eppk_pick_sfair(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint16_t* flow, uint32_t n_flows,
+                    const uint16_t* weight, uint32_t* service, const uint32_t* cost, const uint8_t* band, const eppk_band_table* bands, const uint32_t* cap,
+                    uint32_t cap_all, uint32_t* load, int32_t* out_pick, double* out_score, uint8_t* out_rank) {
+  if (!c || ((!reqs || !out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_sfair: null argument");
+  eppk::BandTab tab;
+  int rc = sfair_check(c, "eppk_pick_sfair", n_reqs, k, bands, n_flows, cost, 0u, &tab);
+  if (rc) return rc;
+  if (n_reqs > c->cfg.max_batch) return fail(c, EPPK_ERR_LIMIT, "eppk_pick_sfair: n_reqs > max_batch");
+  uint32_t counts[EPPK_MAX_BANDS];
+  if ((rc = sfair_host_counts(c, "eppk_pick_sfair", band, flow, n_flows, weight, cost, n_reqs, tab.n_bands, counts))) return rc;
+  if (n_reqs == 0) return EPPK_OK;
+  if ((rc = validate_rows(c, "eppk_pick_sfair", reqs, n_reqs))) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if ((rc = bounded_host_lists(c, reqs, n_reqs, cand_mask, k))) return rc;
+  return sfair_host_finish(c, c->d_tk_pick, c->d_tk_score, n_reqs, k, flow, n_flows, weight, service, cost, band, counts, tab, cap, cap_all, load, out_pick, out_score,
+                           out_rank);
+}
+
 // ---- on-device prompt hashing ------------------------------------------------------------------------
 
 int eppk_hash_prompts_device(eppk_ctx* c, const void* d_prompts, uint64_t prompt_stride, const uint32_t* d_prompt_len,
@@ -4529,6 +4771,33 @@ int eppk_group_pick_wfair(eppk_group* g, const void* reqs, uint32_t n_reqs, cons
       hipMemcpyAsync(c0->d_bd_lscore, totals.data(), totals.size() * 8u, hipMemcpyHostToDevice, c0->stream) != hipSuccess)
     return gfail(g, EPPK_ERR_DEVICE, "eppk_group_pick_wfair: upload failed");
   if ((rc = wfair_host_finish(c0, c0->d_bd_list, c0->d_bd_lscore, n_reqs, k, flow, n_flows, weight, turns, cost, band, counts, tab, cap, cap_all, load, out_pick,
+                              out_score, out_rank)))
+    return mfail(rc);
+  return EPPK_OK;
+}
+
+int eppk_group_pick_sfair(eppk_group* g, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint16_t* flow, uint32_t n_flows,
+                          const uint16_t* weight, uint32_t* service, const uint32_t* cost, const uint8_t* band, const eppk_band_table* bands, const uint32_t* cap,
+                          uint32_t cap_all, uint32_t* load, int32_t* out_pick, double* out_score, uint8_t* out_rank) {
+  if (!g || ((!reqs || !out_pick) && n_reqs)) return gfail(g, EPPK_ERR_ARG, "eppk_group_pick_sfair: null argument");
+  eppk_ctx* c0 = g->ctx[0];
+  eppk::BandTab tab;
+  uint32_t counts[EPPK_MAX_BANDS];
+  int rc = sfair_check(c0, "eppk_group_pick_sfair", n_reqs, k, bands, n_flows, cost, 0u, &tab);
+  if (!rc) rc = sfair_host_counts(c0, "eppk_group_pick_sfair", band, flow, n_flows, weight, cost, n_reqs, tab.n_bands, counts);
+  if (rc) return gfail(g, rc, eppk_last_error(c0));
+  // as eppk_group_pick_bounded: the lists of the whole batch on the host, then ONE resolve on member 0
+  std::vector<int32_t> lists((size_t)n_reqs * k);
+  std::vector<double> totals((size_t)n_reqs * k);
+  if ((rc = group_topk(g, "eppk_group_pick_sfair", reqs, n_reqs, cand_mask, k, false, 0ull, lists.data(), totals.data()))) return rc;
+  if (n_reqs == 0) return EPPK_OK;
+  auto mfail = [&](int code) { return gfail(g, code, "device " + std::to_string(g->dev[0]) + ": " + eppk_last_error(c0)); };
+  if (hipSetDevice(g->dev[0]) != hipSuccess) return gfail(g, EPPK_ERR_DEVICE, "eppk_group_pick_sfair: hipSetDevice failed");
+  if ((rc = bounded_lists(c0, n_reqs))) return mfail(rc);
+  if (hipMemcpyAsync(c0->d_bd_list, lists.data(), lists.size() * 4u, hipMemcpyHostToDevice, c0->stream) != hipSuccess ||
+      hipMemcpyAsync(c0->d_bd_lscore, totals.data(), totals.size() * 8u, hipMemcpyHostToDevice, c0->stream) != hipSuccess)
+    return gfail(g, EPPK_ERR_DEVICE, "eppk_group_pick_sfair: upload failed");
+  if ((rc = sfair_host_finish(c0, c0->d_bd_list, c0->d_bd_lscore, n_reqs, k, flow, n_flows, weight, service, cost, band, counts, tab, cap, cap_all, load, out_pick,
                               out_score, out_rank)))
     return mfail(rc);
   return EPPK_OK;

@@ -862,6 +862,59 @@ class BatchedPicker:
             raise EppkError(rc, "turns_rebase: bad arguments")
         return turns
 
+    # -- ... in cost units: the rows ordered by carried service (SEMANTICS.md §3i) ------------------------
+    def pick_sfair(self, reqs: np.ndarray, k: int, flow, n_flows: int, weight, service, cost, cap, bands=((_lib.EPPK_BOUNDED_SHED, 0),),
+                   band: Optional[np.ndarray] = None, load: Optional[np.ndarray] = None, mask: Optional[np.ndarray] = None
+                   ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray], Optional[np.ndarray]]:
+        """eppk_pick_sfair: pick_wfair with the fairness counted in cost units.  `service` is what every (band, flow) was served in earlier
+        batches, in the units of `cost` (u32 [n_bands][n_flows], None: zeros and nothing handed back); the rows are ordered by start tag,
+        service / weight.  Returns what pick_bounded returns, and the service after this batch (a new array; feed it to the next call, by
+        way of turns_rebase now and then: it works on a service table unchanged)."""
+        reqs = np.ascontiguousarray(reqs, dtype=np.uint64)
+        assert reqs.ndim == 2 and reqs.shape[1] == self.row_words, "request row stride mismatch"
+        R = reqs.shape[0]
+        mptr = None
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint64)
+            assert mask.shape == (R, (self.n_pods + 63) // 64), "mask shape mismatch"
+            mptr = mask.ctypes.data
+        cap_arr, cap_all, load = _bounded_caps(self.n_pods, cap, load)
+        band = _band_bytes(band, R)
+        flow = _flow_words(flow, R)
+        cost = None if cost is None else _cost_words(cost, R)
+        weight, service = _flow_tables(weight, service, len(bands), int(n_flows))
+        picks = np.full(R, -1, dtype=np.int32)
+        scores = np.zeros(R, dtype=np.float64)
+        ranks = np.full(R, _lib.EPPK_RANK_NONE, dtype=np.uint8)
+        self._check(self._lib.eppk_pick_sfair(self._ctx, reqs.ctypes.data, R, mptr, int(k), flow.ctypes.data if flow is not None else None,
+                                              int(n_flows), weight.ctypes.data if weight is not None else None,
+                                              service.ctypes.data if service is not None else None, cost.ctypes.data if cost is not None else None,
+                                              band.ctypes.data if band is not None else None, C.byref(_band_table(bands)),
+                                              cap_arr.ctypes.data if cap_arr is not None else None, cap_all,
+                                              load.ctypes.data if load is not None else None, picks.ctypes.data, scores.ctypes.data,
+                                              ranks.ctypes.data), "pick_sfair")
+        return picks, scores, ranks, load, service
+
+    def pick_sfair_device(self, d_reqs: int, n_reqs: int, d_mask: Optional[int], k: int, d_flow: Optional[int], n_flows: int, d_weight: Optional[int],
+                          d_service: Optional[int], d_cost: Optional[int], d_band: Optional[int], bands, d_cap: Optional[int], cap_all: int,
+                          d_load: Optional[int], d_pick: int, d_score: Optional[int], d_rank: Optional[int], stream: int = 0) -> None:
+        """eppk_pick_sfair_device: device pointers as ints (d_weight: n_flows u16 or None; d_service: n_bands x n_flows u32, in / out, or
+        None), asynchronous on `stream`."""
+        self._check(self._lib.eppk_pick_sfair_device(self._ctx, d_reqs, n_reqs, d_mask or None, int(k), d_flow or None, int(n_flows), d_weight or None,
+                                                     d_service or None, d_cost or None, d_band or None, C.byref(_band_table(bands)), d_cap or None,
+                                                     int(cap_all), d_load or None, d_pick, d_score or None, d_rank or None, stream or None),
+                    "pick_sfair_device")
+
+    def bounded_resolve_sfair_device(self, d_lists: int, d_list_scores: Optional[int], n_reqs: int, k: int, d_flow: Optional[int], n_flows: int,
+                                     d_weight: Optional[int], d_service: Optional[int], d_cost: Optional[int], cost_flags: int, d_band: Optional[int],
+                                     bands, d_cap: Optional[int], cap_all: int, d_load: Optional[int], d_pick: int, d_score: Optional[int],
+                                     d_rank: Optional[int], stream: int = 0) -> None:
+        """eppk_sfair_resolve_device: the service fair resolve alone, over any [n_reqs][k] lists on the device (cost_flags must be 0)."""
+        self._check(self._lib.eppk_sfair_resolve_device(self._ctx, d_lists, d_list_scores or None, n_reqs, int(k), d_flow or None, int(n_flows),
+                                                        d_weight or None, d_service or None, d_cost or None, int(cost_flags), d_band or None,
+                                                        C.byref(_band_table(bands)), d_cap or None, int(cap_all), d_load or None, d_pick,
+                                                        d_score or None, d_rank or None, stream or None), "bounded_resolve_sfair_device")
+
     def bounded_geometry(self) -> Tuple[int, int]:
         """(rows per chunk, the largest batch the one-launch kernel takes) of the bounded resolve (EPPK_BOUND_CHUNK)."""
         out = (C.c_uint32 * 2)()
@@ -1224,6 +1277,29 @@ class DeviceGroup:
                                                     load.ctypes.data if load is not None else None, picks.ctypes.data, scores.ctypes.data,
                                                     ranks.ctypes.data), "group_pick_wfair")
         return picks, scores, ranks, load, turns
+
+    def pick_sfair(self, reqs: np.ndarray, k: int, flow, n_flows: int, weight, service, cost, cap, bands=((_lib.EPPK_BOUNDED_SHED, 0),),
+                   band: Optional[np.ndarray] = None, load: Optional[np.ndarray] = None, mask: Optional[np.ndarray] = None
+                   ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray], Optional[np.ndarray]]:
+        """eppk_group_pick_sfair: BatchedPicker.pick_sfair over the group."""
+        reqs, mask, mptr = self._rows_and_mask(reqs, mask)
+        R = reqs.shape[0]
+        cap_arr, cap_all, load = _bounded_caps(self.n_pods, cap, load)
+        band = _band_bytes(band, R)
+        flow = _flow_words(flow, R)
+        cost = None if cost is None else _cost_words(cost, R)
+        weight, service = _flow_tables(weight, service, len(bands), int(n_flows))
+        picks = np.full(R, -1, dtype=np.int32)
+        scores = np.zeros(R, dtype=np.float64)
+        ranks = np.full(R, _lib.EPPK_RANK_NONE, dtype=np.uint8)
+        self._check(self._lib.eppk_group_pick_sfair(self._g, reqs.ctypes.data, R, mptr, int(k), flow.ctypes.data if flow is not None else None,
+                                                    int(n_flows), weight.ctypes.data if weight is not None else None,
+                                                    service.ctypes.data if service is not None else None, cost.ctypes.data if cost is not None else None,
+                                                    band.ctypes.data if band is not None else None, C.byref(_band_table(bands)),
+                                                    cap_arr.ctypes.data if cap_arr is not None else None, cap_all,
+                                                    load.ctypes.data if load is not None else None, picks.ctypes.data, scores.ctypes.data,
+                                                    ranks.ctypes.data), "group_pick_sfair")
+        return picks, scores, ranks, load, service
 
     # -- the pipelined host path over the group (eppk_group_pick_stage_*) ---------------------------------------------
     def stage_buffers(self, which: int, with_mask: bool = False) -> Tuple[np.ndarray, Optional[np.ndarray]]:

@@ -753,7 +753,7 @@ int eppk_group_pick_fair(eppk_group* g, const void* reqs, uint32_t n_reqs, const
  * score or load and adds the same to the turns handed back.  The *_device forms never wait for the host: d_weight and d_turns are read on
  * the device (once, into the context's own memory) and d_turns is written by the last launch on `stream`.  The notes of the fair forms
  * hold (one stream at a time per context; the scratch grows on demand: that of the fair forms and 100 KiB more); one launch more in
- * front (the copy) and with a d_turns two behind.  Not here: turns in cost units (a turn is a request whatever it costs); a tie-break by
+ * front (the copy) and with a d_turns two behind.  Not here: a tie-break by
  * arrival instead of flow id; assumed load (EPPK_ERR_ARG while it is on, as above).  Errors: as for the fair forms. */
 int eppk_wfair_resolve_device(eppk_ctx* ctx, const int32_t* d_lists, const double* d_list_scores, uint32_t n_reqs, uint32_t k,
                               const uint16_t* d_flow, uint32_t n_flows, const uint16_t* d_weight, uint32_t* d_turns,
@@ -772,6 +772,55 @@ int eppk_pick_wfair(eppk_ctx* ctx, const void* reqs, uint32_t n_reqs, const uint
 /* Over a group, as eppk_group_pick_fair: member 0 resolves; equals eppk_pick_wfair on the unsharded batch bit for bit. */
 int eppk_group_pick_wfair(eppk_group* g, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint16_t* flow,
                           uint32_t n_flows, const uint16_t* weight, uint32_t* turns, const uint32_t* cost, const uint8_t* band,
+                          const eppk_band_table* bands, const uint32_t* cap, uint32_t cap_all, uint32_t* load, int32_t* out_pick,
+                          double* out_score, uint8_t* out_rank);
+
+/* ---- ... in cost units: the rows ordered by carried service (SEMANTICS.md §3i) ------------------------------------------------------
+ * Under the weighted fair entry points above a turn is a request, whatever it costs: a flow of 100 000-token prompts and a flow of
+ * pings take turns one for one, and under cost-weighted caps the first takes nearly all the room.  Here every (band, flow) has the
+ * SERVICE it got in earlier batches, in the cost units of d_cost, d_cap and d_load.  A row is IN THE ORDER as above (band < n_bands,
+ * flow < n_flows, weight[flow] >= 1).  Its CHARGE is its cost if that is 1 .. EPPK_MAX_COST, otherwise 0 (a row with a bad cost is in
+ * the order, holds its place and bids for nothing, as above).  With S = service[band][flow] + the charges of the rows in front of it in
+ * the batch that are in the order with the same (band, flow), its TAG is S / weight[flow] (floor, in 64 bits): the start tag of
+ * start-time fair queuing.  The order of band b is its rows sorted by (tag - the band's least tag, flow, q) ascending, q the row's turn
+ * as above.  Nothing below the order changes.
+ *   d_weight      as above.
+ *   d_service     nullable [n_bands][n_flows] u32, in / out; NULL: zeros, and nothing is reported.  Behind the finish
+ *                 service[b][f] := min(2^32 - 1, service[b][f] + the charges of the rows of (b, f) in the order whose out_pick is not
+ *                 EPPK_NO_PICK): placed and spilled rows count, shed rows and rows without a valid entry do not.
+ *   d_cost        nullable [n_reqs] u32; NULL: every cost is 1.  Per request only: cost_flags must be 0, EPPK_COST_PER_ENTRY returns
+ *                 EPPK_ERR_ARG (the order needs one cost per row before any list is read).
+ *   n_reqs        at most EPPK_SFAIR_MAX_REQS (EPPK_ERR_LIMIT): tag - least tag < 2^32 + n_reqs * 2^24 < 2^42, so the order is exact --
+ *                 no clamp and no saturation anywhere in it.
+ *   every other argument as for the weighted fair entry points.
+ * The result, d_service included, is a pure function of the arguments.  Every cost 1 (or d_cost NULL) is eppk_wfair_resolve_device bit
+ * for bit, the table handed back included; d_weight NULL, d_service NULL and one flow is eppk_costed_resolve_device bit for bit; adding
+ * m * weight[f] to every service[b][f] of a band (without saturation) changes no pick, rank, score or load and adds nothing to the
+ * amounts taken.  eppk_fair_turns_rebase works on a service table unchanged: it rebases in units of table / weight, which is a tag
+ * here as it is a cycle there, and `window` is then the burst an idle flow may claim in cost units per unit of weight.  The *_device
+ * forms never wait for the host; the notes of the weighted fair forms hold.  The order is a stable radix sort on the device (five
+ * passes over the batch, the same cost for any n_flows): about twenty launches in front of the rounds, and with a d_service two behind.
+ * The scratch grows on demand: that of the fair forms, and 24 bytes per request, 8 bytes per chunk and key, 8 KiB per chunk.  Not here:
+ * costs per entry; a one-launch form for small batches; assumed load (EPPK_ERR_ARG while it is on, as above).  Errors: as for the
+ * weighted fair forms, EPPK_ERR_ARG for cost_flags != 0 and EPPK_ERR_LIMIT for n_reqs > EPPK_SFAIR_MAX_REQS. */
+#define EPPK_SFAIR_MAX_REQS 131072u
+int eppk_sfair_resolve_device(eppk_ctx* ctx, const int32_t* d_lists, const double* d_list_scores, uint32_t n_reqs, uint32_t k,
+                              const uint16_t* d_flow, uint32_t n_flows, const uint16_t* d_weight, uint32_t* d_service,
+                              const uint32_t* d_cost, uint32_t cost_flags, const uint8_t* d_band, const eppk_band_table* bands,
+                              const uint32_t* d_cap, uint32_t cap_all, uint32_t* d_load, int32_t* d_out_pick, double* d_out_score,
+                              uint8_t* d_out_rank, void* stream);
+int eppk_pick_sfair_device(eppk_ctx* ctx, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, uint32_t k,
+                           const uint16_t* d_flow, uint32_t n_flows, const uint16_t* d_weight, uint32_t* d_service, const uint32_t* d_cost,
+                           const uint8_t* d_band, const eppk_band_table* bands, const uint32_t* d_cap, uint32_t cap_all, uint32_t* d_load,
+                           int32_t* d_out_pick, double* d_out_score, uint8_t* d_out_rank, void* stream);
+/* Host buffers: weight u16 [n_flows] or NULL, service u32 [n_bands][n_flows] in / out or NULL. */
+int eppk_pick_sfair(eppk_ctx* ctx, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint16_t* flow,
+                    uint32_t n_flows, const uint16_t* weight, uint32_t* service, const uint32_t* cost, const uint8_t* band,
+                    const eppk_band_table* bands, const uint32_t* cap, uint32_t cap_all, uint32_t* load, int32_t* out_pick,
+                    double* out_score, uint8_t* out_rank);
+/* Over a group, as eppk_group_pick_wfair: member 0 resolves; equals eppk_pick_sfair on the unsharded batch bit for bit. */
+int eppk_group_pick_sfair(eppk_group* g, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint16_t* flow,
+                          uint32_t n_flows, const uint16_t* weight, uint32_t* service, const uint32_t* cost, const uint8_t* band,
                           const eppk_band_table* bands, const uint32_t* cap, uint32_t cap_all, uint32_t* load, int32_t* out_pick,
                           double* out_score, uint8_t* out_rank);
 
