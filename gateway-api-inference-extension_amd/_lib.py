@@ -37,6 +37,7 @@ SYMBOLS = [
     "eppk_pick_batch_subset", "eppk_pick_batch_candidates_device",
     "eppk_launch_status", "eppk_pick_random_topk", "eppk_pick_random_topk_device", "eppk_set_assumed_load",
     "eppk_pick_weighted_random", "eppk_pick_weighted_random_device", "eppk_group_pick_weighted_random",
+    "eppk_pick_rendezvous", "eppk_pick_rendezvous_device",
     "eppk_set_filters", "eppk_filter_masks_device", "eppk_filter_masks", "eppk_pick_filtered_device", "eppk_pick_filtered",
     "eppk_bounded_resolve_device", "eppk_pick_bounded_device", "eppk_pick_bounded", "eppk_group_pick_bounded", "eppk_bounded_geometry",
     "eppk_banded_resolve_device", "eppk_pick_banded_device", "eppk_pick_banded", "eppk_group_pick_banded",
@@ -158,6 +159,8 @@ def load_library() -> C.CDLL:
     lib.eppk_pick_random_topk_device.argtypes = [vp, vp, u32, vp, u32, u64, vp, vp, vp]
     lib.eppk_pick_weighted_random.argtypes = [vp, vp, u32, vp, u32, u64, vp, vp]
     lib.eppk_pick_weighted_random_device.argtypes = [vp, vp, u32, vp, u32, u64, vp, vp, vp]
+    lib.eppk_pick_rendezvous.argtypes = [vp, vp, u32, vp, u32, vp, vp, u32, u64, vp, vp]
+    lib.eppk_pick_rendezvous_device.argtypes = [vp, vp, u32, vp, u32, vp, vp, u32, u64, vp, vp, vp]
     lib.eppk_set_assumed_load.argtypes = [vp, u32]
     lib.eppk_set_filters.argtypes = [vp, C.POINTER(FilterProgram), u32]
     lib.eppk_filter_masks_device.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]

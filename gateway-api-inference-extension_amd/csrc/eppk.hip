@@ -15,6 +15,7 @@
 #include "eppk_fair.hip.h"
 #include "eppk_wfair.hip.h"
 #include "eppk_sfair.hip.h"
+#include "eppk_rendezvous.hip.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -242,6 +243,9 @@ struct eppk_ctx {
   DBuf<uint32_t> d_sf_charge;                               // the charge per request (its cost, or 0 for a bad cost)
   DBuf<uint32_t> d_sf_perm;                                 // the second permutation of the sort's ping-pong (the first is d_bn_perm)
   DBuf<uint32_t> d_sf_dh;                                   // total[2048], then [n_chunks][2048]: the digit histogram of a pass
+  // picker "rendezvous" (SEMANTICS.md §3j; eppk_rendezvous.hip.h): what the host form uploads beside the ordered fallbacks' buffers
+  DBuf<uint64_t> d_rv_key;                                  // an affinity key per request (max_batch)
+  DBuf<uint64_t> d_rv_pod;                                  // a key per pod (max_pods)
 
   // measurement
   bool prof = false;
@@ -700,6 +704,35 @@ int launch_wrand(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_
   const uint8_t* reqs8 = (const uint8_t*)d_reqs;
   uint32_t stride = c->stride;
   void* args[] = {&sn, &ix, &ch, &reqs8, &stride, &n_reqs, &pwn, &d_mask, &d_pick, &d_score, &k, &seed, &r0};
+  HIPCHK(c, hipExtLaunchKernel(fn, dim3(grid), dim3(threads), args, lds, st, nullptr, nullptr, 0));
+  c->geom[0] = c->geom[1] = 0u; c->geom[2] = grid; c->geom[3] = threads;
+  c->last_done = nullptr;
+  c->last_stream = st;
+  return EPPK_OK;
+}
+
+// Picker "rendezvous" (SEMANTICS.md §3j): pick_rendezvous_kernel, eight requests per wavefront pass over every candidate, k rounds;
+// d_pick / d_score hold n_reqs * k entries.  Reads no gauge and no index: no epochs, no learn fence.  A persistent grid: as many
+// wavefronts per workgroup as the passes need to give every CU one (16 at most), as many workgroups as fit the CUs this context may use.
+int launch_rendezvous(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_key, uint32_t depth, const uint64_t* d_pod_key,
+                      const uint64_t* d_mask, uint32_t k, uint64_t seed, int32_t* d_pick, double* d_score, hipStream_t st) {
+  const void* fn = d_mask ? (const void*)eppk::pick_rendezvous_kernel<true> : (const void*)eppk::pick_rendezvous_kernel<false>;
+  KSnap sn = make_ksnap(c);
+  const uint32_t n_pass = (n_reqs + eppk::kRdvReqs - 1u) / eppk::kRdvReqs;
+  uint32_t wpb = (n_pass + (uint32_t)c->num_cu - 1u) / (uint32_t)c->num_cu;
+  if (wpb > eppk::kRdvMaxWaves) wpb = eppk::kRdvMaxWaves;
+  if (wpb < 1u) wpb = 1u;
+  const uint32_t threads = wpb * 64u;
+  const size_t lds = eppk::rdv_lds_bytes(sn.J);
+  int occ_per_cu = 1;
+  { const int rco = occupancy_of(c, fn, threads, lds, &occ_per_cu); if (rco) return rco; }
+  uint32_t grid = (n_pass + wpb - 1u) / wpb;
+  const uint32_t cap = (uint32_t)c->num_cu * (uint32_t)occ_per_cu;
+  if (grid > cap) grid = cap;
+  if (grid < 1u) grid = 1u;
+  const uint8_t* reqs8 = (const uint8_t*)d_reqs;
+  uint32_t stride = c->stride;
+  void* args[] = {&sn, &reqs8, &stride, &n_reqs, &d_key, &depth, &d_pod_key, &d_mask, &k, &seed, &d_pick, &d_score};
   HIPCHK(c, hipExtLaunchKernel(fn, dim3(grid), dim3(threads), args, lds, st, nullptr, nullptr, 0));
   c->geom[0] = c->geom[1] = 0u; c->geom[2] = grid; c->geom[3] = threads;
   c->last_done = nullptr;
@@ -2705,6 +2738,56 @@ int eppk_pick_weighted_random(eppk_ctx* c, const void* reqs, uint32_t n_reqs, co
   if (cand_mask) HIPCHK(c, hipMemcpyAsync(c->d_tk_mask, cand_mask, (size_t)n_reqs * J * 8u, hipMemcpyHostToDevice, c->stream));
   rc = run_pick(c, (const uint8_t*)c->d_tk_reqs, n_reqs, cand_mask ? c->d_tk_mask : nullptr, c->d_tk_pick, c->d_tk_score, c->stream, k, false, seed, 0u,
                 nullptr, nullptr, true);
+  if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(out_pick, c->d_tk_pick, (size_t)n_reqs * k * 4u, hipMemcpyDeviceToHost, c->stream));
+  if (out_score) HIPCHK(c, hipMemcpyAsync(out_score, c->d_tk_score, (size_t)n_reqs * k * 8u, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return EPPK_OK;
+}
+
+// ---- picker "rendezvous" (SEMANTICS.md §3j) ---------------------------------------------------------------------------
+
+int eppk_pick_rendezvous_device(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_key, uint32_t depth, const uint64_t* d_pod_key,
+                                const uint64_t* d_cand_mask, uint32_t k, uint64_t seed, int32_t* d_out_pick, double* d_out_score, void* stream) {
+  if (!c || (((!d_reqs && !d_key) || !d_out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_rendezvous_device: null argument");
+  if (k < 1 || k > EPPK_MAX_TOPK) return fail(c, EPPK_ERR_ARG, "eppk_pick_rendezvous_device: k out of range (1..8)");
+  if (!d_key && depth == 0) return fail(c, EPPK_ERR_ARG, "eppk_pick_rendezvous_device: neither keys nor a prefix depth");
+  if (!c->have_snapshot) return fail(c, EPPK_ERR_NO_SNAPSHOT, "eppk_pick_rendezvous_device: no snapshot published");
+  if (n_reqs == 0) return EPPK_OK;
+  if (!d_key && (uint64_t)n_reqs * c->stride >= (1ull << 31)) return fail(c, EPPK_ERR_LIMIT, "eppk_pick_rendezvous_device: batch of 2 GiB and more (split it)");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  return launch_rendezvous(c, d_reqs, n_reqs, d_key, depth, d_pod_key, d_cand_mask, k, seed, d_out_pick, d_out_score, st);
+}
+
+int eppk_pick_rendezvous(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint64_t* key, uint32_t depth, const uint64_t* pod_key,
+                         const uint64_t* cand_mask, uint32_t k, uint64_t seed, int32_t* out_pick, double* out_score) {
+  if (!c || (((!reqs && !key) || !out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_rendezvous: null argument");
+  if (k < 1 || k > EPPK_MAX_TOPK) return fail(c, EPPK_ERR_ARG, "eppk_pick_rendezvous: k out of range (1..8)");
+  if (!key && depth == 0) return fail(c, EPPK_ERR_ARG, "eppk_pick_rendezvous: neither keys nor a prefix depth");
+  if (!c->have_snapshot) return fail(c, EPPK_ERR_NO_SNAPSHOT, "eppk_pick_rendezvous: no snapshot published");
+  if (n_reqs > c->cfg.max_batch) return fail(c, EPPK_ERR_LIMIT, "eppk_pick_rendezvous: n_reqs > max_batch");
+  if (n_reqs == 0) return EPPK_OK;
+  int rc = key ? EPPK_OK : validate_rows(c, "eppk_pick_rendezvous", reqs, n_reqs);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const size_t J = (c->n_pods + 63u) / 64u;
+  if (cand_mask && !J) {
+    for (size_t i = 0; i < (size_t)n_reqs * k; ++i) { out_pick[i] = EPPK_NO_PICK; if (out_score) out_score[i] = 0.0; }
+    return EPPK_OK;
+  }
+  // the buffers of the ordered fallbacks (max_batch x EPPK_MAX_TOPK entries), and the keys' own
+  rc = topk_ensure(c, cand_mask != nullptr);
+  if (!rc && key) rc = ctx_grow(c, c->cfg.max_batch, {{c->d_rv_key, 8u, "rendezvous keys"}});
+  if (!rc && pod_key) rc = ctx_grow(c, c->cfg.max_pods, {{c->d_rv_pod, 8u, "rendezvous pod keys"}});
+  if (rc) return rc;
+  if (key) HIPCHK(c, hipMemcpyAsync(c->d_rv_key, key, (size_t)n_reqs * 8u, hipMemcpyHostToDevice, c->stream));
+  else HIPCHK(c, hipMemcpyAsync(c->d_tk_reqs, reqs, (size_t)n_reqs * c->stride, hipMemcpyHostToDevice, c->stream));
+  if (pod_key && c->n_pods) HIPCHK(c, hipMemcpyAsync(c->d_rv_pod, pod_key, (size_t)c->n_pods * 8u, hipMemcpyHostToDevice, c->stream));
+  if (cand_mask) HIPCHK(c, hipMemcpyAsync(c->d_tk_mask, cand_mask, (size_t)n_reqs * J * 8u, hipMemcpyHostToDevice, c->stream));
+  rc = launch_rendezvous(c, key ? nullptr : (const void*)c->d_tk_reqs, n_reqs, key ? (const uint64_t*)c->d_rv_key : nullptr, depth,
+                         pod_key ? (const uint64_t*)c->d_rv_pod : nullptr, cand_mask ? (const uint64_t*)c->d_tk_mask : nullptr, k, seed,
+                         c->d_tk_pick, c->d_tk_score, c->stream);
   if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(out_pick, c->d_tk_pick, (size_t)n_reqs * k * 4u, hipMemcpyDeviceToHost, c->stream));
   if (out_score) HIPCHK(c, hipMemcpyAsync(out_score, c->d_tk_score, (size_t)n_reqs * k * 8u, hipMemcpyDeviceToHost, c->stream));

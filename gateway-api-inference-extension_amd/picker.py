@@ -561,6 +561,46 @@ class BatchedPicker:
         self._check(self._lib.eppk_pick_weighted_random_device(self._ctx, d_reqs, n_reqs, d_mask, int(k), seed & 0xFFFFFFFFFFFFFFFF, d_pick, d_score,
                                                                stream or None), "pick_weighted_random_device")
 
+    def pick_rendezvous(self, reqs: Optional[np.ndarray], k: int, seed: int, key: Optional[np.ndarray] = None, depth: int = 0,
+                        pod_key: Optional[np.ndarray] = None, mask: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """Picker "rendezvous" (SEMANTICS.md §3j): each request's candidates ordered by a hash of (affinity key, pod key), the first k.
+        key [R] u64 = the session form (reqs may be None); key None = the prefix form, the key is block hash min(depth, n_blocks) of
+        the row.  pod_key [n_pods] u64 (None: the slot index).  ([R, k] candidate indices, [R, k] h * 2^-32)."""
+        if not 1 <= int(k) <= 8:
+            raise EppkError(-1, "pick_rendezvous: k out of range (1..8)")
+        rptr = kptr = pptr = mptr = None
+        if key is not None:
+            key = np.ascontiguousarray(key, dtype=np.uint64)
+            assert key.ndim == 1, "one key per request"
+            R, kptr = key.shape[0], key.ctypes.data
+        if reqs is not None:
+            reqs = np.ascontiguousarray(reqs, dtype=np.uint64)
+            assert reqs.ndim == 2 and reqs.shape[1] == self.row_words, "request row stride mismatch"
+            assert key is None or reqs.shape[0] == R, "one key per request row"
+            R, rptr = reqs.shape[0], reqs.ctypes.data
+        if key is None and reqs is None:
+            raise EppkError(-1, "pick_rendezvous: neither keys nor request rows")
+        if pod_key is not None:
+            pod_key = np.ascontiguousarray(pod_key, dtype=np.uint64)
+            assert pod_key.shape == (self.n_pods,), "one key per published pod"
+            pptr = pod_key.ctypes.data
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint64)
+            assert mask.shape == (R, (self.n_pods + 63) // 64), "mask shape mismatch"
+            mptr = mask.ctypes.data
+        picks = np.full((R, k), -1, dtype=np.int32)
+        scores = np.zeros((R, k), dtype=np.float64)
+        self._check(self._lib.eppk_pick_rendezvous(self._ctx, rptr, R, kptr, int(depth), pptr, mptr, int(k), seed & 0xFFFFFFFFFFFFFFFF,
+                                                   picks.ctypes.data, scores.ctypes.data), "pick_rendezvous")
+        return picks, scores
+
+    def pick_rendezvous_device(self, d_reqs: Optional[int], n_reqs: int, k: int, seed: int, d_pick: int, d_score: Optional[int],
+                               d_key: Optional[int] = None, depth: int = 0, d_pod_key: Optional[int] = None, d_mask: Optional[int] = None,
+                               stream: int = 0) -> None:
+        """eppk_pick_rendezvous_device: n_reqs * k entries at d_pick / d_score, asynchronous on `stream` (0 = the context's)."""
+        self._check(self._lib.eppk_pick_rendezvous_device(self._ctx, d_reqs, n_reqs, d_key, int(depth), d_pod_key, d_mask, int(k),
+                                                          seed & 0xFFFFFFFFFFFFFFFF, d_pick, d_score, stream or None), "pick_rendezvous_device")
+
     # -- metric predicates of the Filter phase (SEMANTICS.md §2c) ----------------------------------
     def set_filters(self, programs: Sequence[Sequence[Tuple]]) -> None:
         """programs: up to 4 lists of up to 4 stages (kind, on_empty, threshold); the threshold is the u32 `u` of the integer kinds and

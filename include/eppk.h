@@ -386,6 +386,31 @@ int eppk_pick_weighted_random(eppk_ctx* ctx, const void* reqs, uint32_t n_reqs, 
 int eppk_pick_weighted_random_device(eppk_ctx* ctx, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, uint32_t k,
                                      uint64_t seed, int32_t* d_out_pick, double* d_out_score, void* stream);
 
+/* Picker "rendezvous" (highest-random-weight hashing; docs/proposals/0602-prefix-cache-aware-routing-proposal/README.md:39-65 session
+ * affinity and prefix-affinity consistent hashing, :129 "use the consistent hashing strategy to improve the predictability of two EPPs
+ * picking the same server"; SEMANTICS.md §3j): the list of request r is its candidates (cand_mask AND not a hole, as every pick) sorted
+ * by h(r, p) = fmix32(fold(splitmix64(key[r] + seed * 0x9E3779B97F4A7C15)) ^ fold(splitmix64(pod_key[p]))) descending, ties by p
+ * ascending, cut at k (1..EPPK_MAX_TOPK) and padded with EPPK_NO_PICK / 0.0; out_score (nullable) is h * 2^-32, exact and in [0, 1).
+ * The answer depends on the keys alone -- no gauge, no index, no assumed load (legal while eppk_set_assumed_load is on; nothing is
+ * bumped) -- so two gateways that hash the same endpoint addresses agree, and a pod that leaves (hole or mask) moves only the
+ * requests that had it in their list.
+ *   key      [n_reqs] affinity keys (a hash of the session header): the SESSION form; reqs is not read and may be NULL.
+ *   key NULL the PREFIX form: key[r] = hash[min(depth, n_blocks) - 1] of request row r (the chained block hash: it names the whole prefix
+ *            up to that block), 0 for a row without blocks; depth >= 1 (depth 0 without keys: EPPK_ERR_ARG).  Rows are checked as
+ *            for eppk_pick_topk (host form: EPPK_ERR_ARG names the row; device form: EPPK_NO_PICK entries and
+ *            EPPK_LAUNCH_BAD_REQUEST_ROW).
+ *   pod_key  [n_pods] a key per endpoint slot (a hash of its address: the answer then does not depend on the slot); NULL: the slot index.
+ * The lists and scores are d_lists / d_list_scores of every resolve: consistent hashing with bounded loads is
+ * eppk_pick_rendezvous_device followed by eppk_bounded_resolve_device(EPPK_BOUNDED_SPILL) on one stream.  Needs a published snapshot
+ * (EPPK_ERR_NO_SNAPSHOT); n_reqs > max_batch is EPPK_ERR_LIMIT on the host form, a prefix-form batch of 2 GiB and more on the device
+ * form.  The host form uploads keys, pod keys, rows and mask, runs the kernel and waits; the device form is asynchronous on `stream`
+ * (NULL = the context's).  Cost: DESIGN.md §3.19. */
+int eppk_pick_rendezvous(eppk_ctx* ctx, const void* reqs, uint32_t n_reqs, const uint64_t* key, uint32_t depth, const uint64_t* pod_key,
+                         const uint64_t* cand_mask, uint32_t k, uint64_t seed, int32_t* out_pick, double* out_score);
+int eppk_pick_rendezvous_device(eppk_ctx* ctx, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_key, uint32_t depth,
+                                const uint64_t* d_pod_key, const uint64_t* d_cand_mask, uint32_t k, uint64_t seed, int32_t* d_out_pick,
+                                double* d_out_score, void* stream);
+
 /* Assumed load (docs/proposals/006-scheduler/README.md:154-156; SEMANTICS.md §2b).  epochs = E >= 1: every batch handed to a pick
  * entry point of this context is scored in E epochs of ceil(n_reqs / E) consecutive requests; after each epoch the queue gauge of
  * every picked endpoint grows by one per request routed to it and everything derived from the gauge is rebuilt on the device
