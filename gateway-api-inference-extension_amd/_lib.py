@@ -42,6 +42,7 @@ SYMBOLS = [
     "eppk_bounded_resolve_device", "eppk_pick_bounded_device", "eppk_pick_bounded", "eppk_group_pick_bounded", "eppk_bounded_geometry",
     "eppk_banded_resolve_device", "eppk_pick_banded_device", "eppk_pick_banded", "eppk_group_pick_banded",
     "eppk_costed_resolve_device", "eppk_pick_costed_device", "eppk_pick_costed", "eppk_group_pick_costed",
+    "eppk_prefix_costs_device", "eppk_prefix_costs", "eppk_pick_cost_cached_device", "eppk_pick_cost_cached",
     "eppk_fair_resolve_device", "eppk_pick_fair_device", "eppk_pick_fair", "eppk_group_pick_fair",
     "eppk_wfair_resolve_device", "eppk_pick_wfair_device", "eppk_pick_wfair", "eppk_group_pick_wfair", "eppk_fair_turns_rebase",
     "eppk_sfair_resolve_device", "eppk_pick_sfair_device", "eppk_pick_sfair", "eppk_group_pick_sfair",
@@ -180,6 +181,10 @@ def load_library() -> C.CDLL:
     lib.eppk_pick_costed_device.argtypes = [vp, vp, u32, vp, u32, vp, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp, vp]
     lib.eppk_pick_costed.argtypes = [vp, vp, u32, vp, u32, vp, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp]
     lib.eppk_group_pick_costed.argtypes = [vp, vp, u32, vp, u32, vp, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp]
+    lib.eppk_prefix_costs_device.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, vp, vp]
+    lib.eppk_prefix_costs.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, vp]
+    lib.eppk_pick_cost_cached_device.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp, vp]
+    lib.eppk_pick_cost_cached.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp]
     lib.eppk_fair_resolve_device.argtypes = [vp, vp, vp, u32, u32, vp, u32, vp, u32, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp, vp]
     lib.eppk_pick_fair_device.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp, vp]
     lib.eppk_pick_fair.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp]

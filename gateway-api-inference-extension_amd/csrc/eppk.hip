@@ -16,6 +16,7 @@
 #include "eppk_wfair.hip.h"
 #include "eppk_sfair.hip.h"
 #include "eppk_rendezvous.hip.h"
+#include "eppk_prefix_costs.hip.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -246,6 +247,11 @@ struct eppk_ctx {
   // picker "rendezvous" (SEMANTICS.md §3j; eppk_rendezvous.hip.h): what the host form uploads beside the ordered fallbacks' buffers
   DBuf<uint64_t> d_rv_key;                                  // an affinity key per request (max_batch)
   DBuf<uint64_t> d_rv_pod;                                  // a key per pod (max_pods)
+  // costs per list entry from the prefix index (SEMANTICS.md §3k; eppk_prefix_costs.hip.h): one group, a row per request
+  DBuf<int32_t> d_pc_list;                                  // [rows][EPPK_MAX_TOPK] the lists a host form uploads
+  DBuf<uint32_t> d_pc_base;                                 // [rows] the full costs a host form uploads
+  DBuf<uint32_t> d_pc_cost;                                 // [rows][EPPK_MAX_TOPK] costs: what eppk_pick_cost_cached hands its resolve
+  DBuf<uint32_t> d_pc_matched;                              // [rows][EPPK_MAX_TOPK] matched blocks (host form)
 
   // measurement
   bool prof = false;
@@ -735,6 +741,43 @@ int launch_rendezvous(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const ui
   void* args[] = {&sn, &reqs8, &stride, &n_reqs, &d_key, &depth, &d_pod_key, &d_mask, &k, &seed, &d_pick, &d_score};
   HIPCHK(c, hipExtLaunchKernel(fn, dim3(grid), dim3(threads), args, lds, st, nullptr, nullptr, 0));
   c->geom[0] = c->geom[1] = 0u; c->geom[2] = grid; c->geom[3] = threads;
+  c->last_done = nullptr;
+  c->last_stream = st;
+  return EPPK_OK;
+}
+
+// Costs per list entry (SEMANTICS.md §3k): prefix_costs_kernel, a group of G lanes per request (G from max_blocks: 64 / G requests per
+// wavefront pass), one lane per block.  Reads the index: ordered behind a LEARN batch's update as a pick is.  A persistent grid of
+// 256-thread workgroups, as many as fit the CUs this context may use; always a launch (no resident form).
+int launch_prefix_costs(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const int32_t* d_lists, uint32_t k, const uint32_t* d_base, uint32_t unit,
+                        uint32_t* d_cost, uint32_t* d_matched, hipStream_t st) {
+  { const int rcf = learn_fence(c, st); if (rcf) return rcf; }
+  const uint32_t G = eppk::pc_group(c->cfg.max_blocks);
+  const void* fn = nullptr;
+  by_lane_word(c, [&](auto tag) {
+    using LW = decltype(tag);
+    fn = G == 16u ? (const void*)eppk::prefix_costs_kernel<LW, 16u> : G == 32u ? (const void*)eppk::prefix_costs_kernel<LW, 32u>
+                                                                              : (const void*)eppk::prefix_costs_kernel<LW, 64u>;
+    return 0;
+  });
+  KSnap sn = make_ksnap(c);
+  KIndex ix = make_kindex(c);
+  const uint32_t wpb = eppk::kPcThreads / 64u, per_pass = 64u / G;
+  const uint32_t n_pass = (n_reqs + per_pass - 1u) / per_pass;
+  int occ_per_cu = 1;
+  { const int rco = occupancy_of(c, fn, eppk::kPcThreads, 0, &occ_per_cu); if (rco) return rco; }
+  uint32_t grid = (n_pass + wpb - 1u) / wpb;
+  const uint32_t cap = (uint32_t)c->num_cu * (uint32_t)occ_per_cu;
+  if (grid > cap) grid = cap;
+  if (grid < 1u) grid = 1u;
+  const uint8_t* reqs8 = (const uint8_t*)d_reqs;
+  uint32_t stride = c->stride;
+  const uint64_t* nat = sn.nat;
+  uint32_t n_pods = sn.n_pods;
+  uint32_t* status = sn.status;
+  void* args[] = {&nat, &n_pods, &status, &ix, &reqs8, &stride, &n_reqs, &d_lists, &k, &d_base, &unit, &d_cost, &d_matched};
+  HIPCHK(c, hipExtLaunchKernel(fn, dim3(grid), dim3(eppk::kPcThreads), args, 0, st, nullptr, nullptr, 0));
+  c->geom[0] = c->geom[1] = 0u; c->geom[2] = grid; c->geom[3] = eppk::kPcThreads;
   c->last_done = nullptr;
   c->last_stream = st;
   return EPPK_OK;
@@ -3468,6 +3511,124 @@ int eppk_pick_costed(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint6
   HIPCHK(c, hipSetDevice(c->cfg.device));
   if ((rc = bounded_host_lists(c, reqs, n_reqs, cand_mask, k))) return rc;
   return costed_host_finish(c, c->d_tk_pick, c->d_tk_score, n_reqs, k, cost, band, counts, tab, cap, cap_all, load, out_pick, out_score, out_rank);
+}
+
+// ---- costs per list entry from the prefix index (SEMANTICS.md §3k; eppk_prefix_costs.hip.h) ---------------------------------------
+
+namespace {
+
+int prefix_costs_check(eppk_ctx* c, const char* who, uint32_t k, uint32_t unit) {
+  if (k < 1 || k > EPPK_MAX_TOPK) return fail(c, EPPK_ERR_ARG, std::string(who) + ": k out of range (1..8)");
+  if (unit == 0) return fail(c, EPPK_ERR_ARG, std::string(who) + ": unit 0 (cost units saved per matched block, >= 1)");
+  if (!c->have_snapshot) return fail(c, EPPK_ERR_NO_SNAPSHOT, std::string(who) + ": no snapshot published");
+  return EPPK_OK;
+}
+
+int prefix_costs_buffers(eppk_ctx* c, uint32_t n_reqs) {
+  return ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_pc_list, EPPK_MAX_TOPK * 4u, "prefix costs: lists"}, {c->d_pc_base, 4u, "prefix costs: full costs"},
+                                               {c->d_pc_cost, EPPK_MAX_TOPK * 4u, "prefix costs: costs"}, {c->d_pc_matched, EPPK_MAX_TOPK * 4u, "prefix costs: matched blocks"}});
+}
+
+// The full cost of every row of a host form, as the kernel will see it (base NULL: n_blocks * unit inside 1 .. 2^32 - 1).
+void prefix_costs_host_base(const eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint32_t* base, uint32_t unit, std::vector<uint32_t>* out) {
+  out->resize(n_reqs);
+  for (uint32_t r = 0; r < n_reqs; ++r) {
+    eppk_req_hdr h;
+    std::memcpy(&h, (const uint8_t*)reqs + (size_t)r * c->stride, sizeof h);
+    const uint64_t b64 = (uint64_t)h.n_blocks * unit;
+    (*out)[r] = base ? base[r] : b64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : b64 ? (uint32_t)b64 : 1u;
+  }
+}
+
+}  // namespace
+
+int eppk_prefix_costs_device(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const int32_t* d_lists, uint32_t k, const uint32_t* d_base, uint32_t unit,
+                             uint32_t* d_out_cost, uint32_t* d_out_matched, void* stream) {
+  if (!c || ((!d_reqs || !d_lists) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_prefix_costs_device: null argument");
+  if (!d_out_cost && !d_out_matched) return fail(c, EPPK_ERR_ARG, "eppk_prefix_costs_device: neither costs nor matched blocks asked for");
+  const int rc = prefix_costs_check(c, "eppk_prefix_costs_device", k, unit);
+  if (rc) return rc;
+  if (n_reqs == 0) return EPPK_OK;
+  if ((uint64_t)n_reqs * c->stride >= (1ull << 31)) return fail(c, EPPK_ERR_LIMIT, "eppk_prefix_costs_device: batch of 2 GiB and more (split it)");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  return launch_prefix_costs(c, d_reqs, n_reqs, d_lists, k, d_base, unit, d_out_cost, d_out_matched, stream ? (hipStream_t)stream : c->stream);
+}
+
+int eppk_prefix_costs(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const int32_t* lists, uint32_t k, const uint32_t* base, uint32_t unit,
+                      uint32_t* out_cost, uint32_t* out_matched) {
+  if (!c || ((!reqs || !lists) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_prefix_costs: null argument");
+  if (!out_cost && !out_matched) return fail(c, EPPK_ERR_ARG, "eppk_prefix_costs: neither costs nor matched blocks asked for");
+  int rc = prefix_costs_check(c, "eppk_prefix_costs", k, unit);
+  if (rc) return rc;
+  if (n_reqs > c->cfg.max_batch) return fail(c, EPPK_ERR_LIMIT, "eppk_prefix_costs: n_reqs > max_batch");
+  if (n_reqs == 0) return EPPK_OK;
+  if ((rc = validate_rows(c, "eppk_prefix_costs", reqs, n_reqs))) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if ((rc = topk_ensure(c, false))) return rc;
+  if ((rc = prefix_costs_buffers(c, n_reqs))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->d_tk_reqs, reqs, (size_t)n_reqs * c->stride, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_pc_list, lists, (size_t)n_reqs * k * 4u, hipMemcpyHostToDevice, c->stream));
+  if (base) HIPCHK(c, hipMemcpyAsync(c->d_pc_base, base, (size_t)n_reqs * 4u, hipMemcpyHostToDevice, c->stream));
+  if ((rc = launch_prefix_costs(c, c->d_tk_reqs, n_reqs, c->d_pc_list, k, base ? (const uint32_t*)c->d_pc_base : nullptr, unit, c->d_pc_cost, c->d_pc_matched,
+                                c->stream))) return rc;
+  if (out_cost) HIPCHK(c, hipMemcpyAsync(out_cost, c->d_pc_cost, (size_t)n_reqs * k * 4u, hipMemcpyDeviceToHost, c->stream));
+  if (out_matched) HIPCHK(c, hipMemcpyAsync(out_matched, c->d_pc_matched, (size_t)n_reqs * k * 4u, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return EPPK_OK;
+}
+
+// eppk_pick_costed with the costs of §3k: the ordered fallbacks, prefix_costs_kernel over them into d_pc_cost, the costed resolve per entry.
+int eppk_pick_cost_cached_device(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, uint32_t k, const uint32_t* d_base,
+                                   uint32_t unit, const uint8_t* d_band, const eppk_band_table* bands, const uint32_t* d_cap, uint32_t cap_all,
+                                   uint32_t* d_load, int32_t* d_out_pick, double* d_out_score, uint8_t* d_out_rank, void* stream) {
+  if (!c || ((!d_reqs || !d_out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_cost_cached_device: null argument");
+  eppk::BandTab tab;
+  int rc = banded_check(c, "eppk_pick_cost_cached_device", k, bands, &tab);
+  if (rc) return rc;
+  if ((rc = prefix_costs_check(c, "eppk_pick_cost_cached_device", k, unit))) return rc;
+  if (n_reqs == 0) return EPPK_OK;
+  if ((uint64_t)n_reqs * c->stride >= (1ull << 31)) return fail(c, EPPK_ERR_LIMIT, "eppk_pick_cost_cached_device: batch of 2 GiB and more (split it)");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  if ((rc = bounded_lists(c, n_reqs))) return rc;
+  if ((rc = prefix_costs_buffers(c, n_reqs))) return rc;
+  if ((rc = eppk_pick_topk_device(c, d_reqs, n_reqs, d_cand_mask, k, c->d_bd_list, c->d_bd_lscore, stream))) return rc;
+  if ((rc = launch_prefix_costs(c, d_reqs, n_reqs, c->d_bd_list, k, d_base, unit, c->d_pc_cost, nullptr, st))) return rc;
+  return costed_resolve(c, c->d_bd_list, c->d_bd_lscore, n_reqs, k, c->d_pc_cost, EPPK_COST_PER_ENTRY, d_band, tab, nullptr, d_cap, cap_all, d_load, d_out_pick,
+                        d_out_score, d_out_rank, st);
+}
+
+int eppk_pick_cost_cached(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint32_t* base, uint32_t unit,
+                            const uint8_t* band, const eppk_band_table* bands, const uint32_t* cap, uint32_t cap_all, uint32_t* load, int32_t* out_pick,
+                            double* out_score, uint8_t* out_rank) {
+  if (!c || ((!reqs || !out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_cost_cached: null argument");
+  eppk::BandTab tab;
+  int rc = banded_check(c, "eppk_pick_cost_cached", k, bands, &tab);
+  if (rc) return rc;
+  if ((rc = prefix_costs_check(c, "eppk_pick_cost_cached", k, unit))) return rc;
+  if (n_reqs > c->cfg.max_batch) return fail(c, EPPK_ERR_LIMIT, "eppk_pick_cost_cached: n_reqs > max_batch");
+  if (n_reqs == 0) return EPPK_OK;
+  if ((rc = validate_rows(c, "eppk_pick_cost_cached", reqs, n_reqs))) return rc;
+  std::vector<uint32_t> full;                      // band bytes and full costs checked as eppk_pick_costed checks its costs: the lowest bad row is named
+  prefix_costs_host_base(c, reqs, n_reqs, base, unit, &full);
+  uint32_t counts[EPPK_MAX_BANDS];
+  if ((rc = costed_host_counts(c, "eppk_pick_cost_cached", band, full.data(), n_reqs, tab.n_bands, counts))) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if ((rc = bounded_host_lists(c, reqs, n_reqs, cand_mask, k))) return rc;
+  if ((rc = prefix_costs_buffers(c, n_reqs))) return rc;
+  if (band) {
+    if ((rc = ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_bn_band, 1u, "banded picker: bands"}}))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_bn_band, band, n_reqs, hipMemcpyHostToDevice, c->stream));
+  }
+  HIPCHK(c, hipMemcpyAsync(c->d_pc_base, full.data(), (size_t)n_reqs * 4u, hipMemcpyHostToDevice, c->stream));
+  const size_t J = (c->n_pods + 63u) / 64u;
+  if (cand_mask && !J) HIPCHK(c, hipMemcpyAsync(c->d_tk_reqs, reqs, (size_t)n_reqs * c->stride, hipMemcpyHostToDevice, c->stream));   // (bounded_host_lists uploaded no rows)
+  if ((rc = launch_prefix_costs(c, c->d_tk_reqs, n_reqs, c->d_tk_pick, k, c->d_pc_base, unit, c->d_pc_cost, nullptr, c->stream))) return rc;
+  return bounded_host_around(c, n_reqs, cap, load, out_pick, out_score, out_rank,
+                             [&](const uint32_t* d_cap, uint32_t* d_load, int32_t* d_pick, double* d_score, uint8_t* d_rank) {
+                               return costed_resolve(c, c->d_tk_pick, c->d_tk_score, n_reqs, k, c->d_pc_cost, EPPK_COST_PER_ENTRY, band ? c->d_bn_band : nullptr, tab,
+                                                     counts, d_cap, cap_all, d_load, d_pick, d_score, d_rank, c->stream);
+                             });
 }
 
 // ---- ... with fair shares between flows (SEMANTICS.md §3g; eppk_fair.hip.h) ------------------------------------------------------

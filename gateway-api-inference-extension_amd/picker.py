@@ -792,6 +792,65 @@ class BatchedPicker:
                                                          d_band or None, C.byref(_band_table(bands)), d_cap or None, int(cap_all), d_load or None,
                                                          d_pick, d_score or None, d_rank or None, stream or None), "bounded_resolve_costed_device")
 
+    # -- costs per list entry from the prefix index (SEMANTICS.md §3k) --------------------------------
+    def prefix_costs(self, reqs: np.ndarray, lists: np.ndarray, unit: int = 1, base=None) -> Tuple[np.ndarray, np.ndarray]:
+        """eppk_prefix_costs: for every entry of `lists` (i32 [R, k]) the leading blocks of the request that the index holds for that
+        pod, and the cost that is left: max(1, base - min(base, matched * unit)); `base` None: n_blocks * unit.
+        ([R, k] u32 costs, [R, k] u32 matched blocks)."""
+        reqs = np.ascontiguousarray(reqs, dtype=np.uint64)
+        assert reqs.ndim == 2 and reqs.shape[1] == self.row_words, "request row stride mismatch"
+        lists = np.ascontiguousarray(lists, dtype=np.int32)
+        R = reqs.shape[0]
+        assert lists.ndim == 2 and lists.shape[0] == R, "one list per request row"
+        k = lists.shape[1]
+        base = None if base is None else _cost_words(base, R)
+        cost = np.zeros((R, k), dtype=np.uint32)
+        matched = np.zeros((R, k), dtype=np.uint32)
+        self._check(self._lib.eppk_prefix_costs(self._ctx, reqs.ctypes.data, R, lists.ctypes.data, k, base.ctypes.data if base is not None else None,
+                                                int(unit), cost.ctypes.data, matched.ctypes.data), "prefix_costs")
+        return cost, matched
+
+    def prefix_costs_device(self, d_reqs: int, n_reqs: int, d_lists: int, k: int, d_base: Optional[int], unit: int, d_cost: Optional[int],
+                            d_matched: Optional[int], stream: int = 0) -> None:
+        """eppk_prefix_costs_device: n_reqs * k u32 at d_cost / d_matched (either may be None), asynchronous on `stream`."""
+        self._check(self._lib.eppk_prefix_costs_device(self._ctx, d_reqs, n_reqs, d_lists, int(k), d_base or None, int(unit), d_cost or None,
+                                                       d_matched or None, stream or None), "prefix_costs_device")
+
+    def pick_costed_cached(self, reqs: np.ndarray, k: int, cap, unit: int = 1, base=None, bands=((_lib.EPPK_BOUNDED_SHED, 0),),
+                           band: Optional[np.ndarray] = None, load: Optional[np.ndarray] = None, mask: Optional[np.ndarray] = None
+                           ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray]]:
+        """eppk_pick_cost_cached: pick_bounded_costed where a request costs, on each entry of its list, only the blocks that pod
+        does not hold (prefix_costs over the ordered fallbacks).  Returns what pick_bounded returns."""
+        reqs = np.ascontiguousarray(reqs, dtype=np.uint64)
+        assert reqs.ndim == 2 and reqs.shape[1] == self.row_words, "request row stride mismatch"
+        R = reqs.shape[0]
+        mptr = None
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint64)
+            assert mask.shape == (R, (self.n_pods + 63) // 64), "mask shape mismatch"
+            mptr = mask.ctypes.data
+        cap_arr, cap_all, load = _bounded_caps(self.n_pods, cap, load)
+        band = _band_bytes(band, R)
+        base = None if base is None else _cost_words(base, R)
+        picks = np.full(R, -1, dtype=np.int32)
+        scores = np.zeros(R, dtype=np.float64)
+        ranks = np.full(R, _lib.EPPK_RANK_NONE, dtype=np.uint8)
+        self._check(self._lib.eppk_pick_cost_cached(self._ctx, reqs.ctypes.data, R, mptr, int(k), base.ctypes.data if base is not None else None,
+                                                      int(unit), band.ctypes.data if band is not None else None, C.byref(_band_table(bands)),
+                                                      cap_arr.ctypes.data if cap_arr is not None else None, cap_all,
+                                                      load.ctypes.data if load is not None else None, picks.ctypes.data, scores.ctypes.data,
+                                                      ranks.ctypes.data), "pick_costed_cached")
+        return picks, scores, ranks, load
+
+    def pick_costed_cached_device(self, d_reqs: int, n_reqs: int, d_mask: Optional[int], k: int, d_base: Optional[int], unit: int,
+                                  d_band: Optional[int], bands, d_cap: Optional[int], cap_all: int, d_load: Optional[int], d_pick: int,
+                                  d_score: Optional[int], d_rank: Optional[int], stream: int = 0) -> None:
+        """eppk_pick_cost_cached_device: device pointers as ints (d_base: n_reqs u32 or None), asynchronous on `stream`."""
+        self._check(self._lib.eppk_pick_cost_cached_device(self._ctx, d_reqs, n_reqs, d_mask or None, int(k), d_base or None, int(unit),
+                                                             d_band or None, C.byref(_band_table(bands)), d_cap or None, int(cap_all),
+                                                             d_load or None, d_pick, d_score or None, d_rank or None, stream or None),
+                    "pick_costed_cached_device")
+
     # -- ... with fair shares between flows (SEMANTICS.md §3g) ----------------------------------------
     def pick_bounded_fair(self, reqs: np.ndarray, k: int, flow, n_flows: int, cost, cap, bands=((_lib.EPPK_BOUNDED_SHED, 0),),
                           band: Optional[np.ndarray] = None, load: Optional[np.ndarray] = None, mask: Optional[np.ndarray] = None

@@ -682,7 +682,7 @@ int eppk_group_pick_banded(eppk_group* g, const void* reqs, uint32_t n_reqs, con
  *                 EPPK_NO_PICK / 0.0 / EPPK_RANK_NONE and raises EPPK_LAUNCH_BAD_REQUEST_ROW (its list is still checked for
  *                 EPPK_LAUNCH_BAD_PICK); the host-buffer forms refuse the batch with EPPK_ERR_ARG and name the lowest such row.
  *   d_band NULL and a one-band table give the cost form of the plain bounded resolve.  Every other argument as above; the pick forms
- *   take per-request costs only (the caller cannot know the lists).
+ *   take per-request costs only (the caller cannot know the lists; eppk_pick_cost_cached below charges per entry from the index).
  * The same notes hold: asynchronous on `stream`; ONE stream at a time per context for the bounded, banded and costed entry points; the
  * scratch (as above, and the takers' totals per pod) grows on demand: a call that replaces it drains the DEVICE first, a first call
  * allocates it; neither is asynchronous or can be captured into a graph.  A batch of at most one chunk takes a single launch; a larger one is put in band
@@ -706,6 +706,42 @@ int eppk_pick_costed(eppk_ctx* ctx, const void* reqs, uint32_t n_reqs, const uin
 int eppk_group_pick_costed(eppk_group* g, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k, const uint32_t* cost,
                            const uint8_t* band, const eppk_band_table* bands, const uint32_t* cap, uint32_t cap_all, uint32_t* load,
                            int32_t* out_pick, double* out_score, uint8_t* out_rank);
+
+/* ---- costs per list entry from the prefix index: charge the uncached blocks only (SEMANTICS.md §3k) ----------------------------
+ * The caller of the pick forms above "cannot know the lists", and nobody outside the library can know which blocks of a prompt a pod
+ * holds: the approximate prefix index lives on the device.  These calls answer exactly that, per list entry.  For request row r and
+ * entry j with p = lists[r][j]: stop(r) is the first i < n_blocks whose hash[i] the index does not hold (n_blocks if none), and
+ *   matched[r][j] = |{ i < stop(r) : p in index[hash[i]] }|
+ * -- the matched[p] of the PREFIX scorer (SEMANTICS.md §3), over all pods: candidate masks play no part.  matched is 0 for an entry
+ * that is no pod of the snapshot (EPPK_NO_PICK, negative, >= n_pods), for a hole, in a context with index_slots = 0, and for a row out of
+ * range (checked as for eppk_pick_topk: the host form refuses the batch with EPPK_ERR_ARG and names the row; the device form raises
+ * EPPK_LAUNCH_BAD_REQUEST_ROW).  Then
+ *   cost[r][j] = max(1, base[r] - min(base[r], matched[r][j] * unit))        (in 64 bits)
+ *   unit     >= 1 (0: EPPK_ERR_ARG): the cost units one matched block saves.
+ *   base     [n_reqs] the full cost of request r; NULL: n_blocks[r] * unit, inside 1 .. 2^32 - 1 (a row without blocks costs 1).  A
+ *            base[r] outside 1 .. EPPK_MAX_COST is copied to every entry unchanged: the resolve behind reports the row as it always did.
+ *   lists    i32 [n_reqs][k], k in 1 .. EPPK_MAX_TOPK: what any pick wrote, or the caller's own.
+ *   out_cost, out_matched   u32 [n_reqs][k], each nullable, not both (EPPK_ERR_ARG).  out_cost is d_cost of eppk_costed_resolve_device under
+ *            EPPK_COST_PER_ENTRY.
+ * Needs a published snapshot (EPPK_ERR_NO_SNAPSHOT); n_reqs > max_batch is EPPK_ERR_LIMIT on the host form, a batch of 2 GiB and more
+ * on the device form.  The device form is asynchronous on `stream` (NULL = the context's) and READS THE INDEX: the ordering rules are
+ * those of eppk_pick_batch_device (behind index updates on the same stream).  Always launches (also under EPPK_RESIDENT=1); reads no
+ * gauge: legal while eppk_set_assumed_load is on, bumps nothing.  Cost: DESIGN.md §3.20. */
+int eppk_prefix_costs_device(eppk_ctx* ctx, const void* d_reqs, uint32_t n_reqs, const int32_t* d_lists, uint32_t k,
+                             const uint32_t* d_base, uint32_t unit, uint32_t* d_out_cost, uint32_t* d_out_matched, void* stream);
+int eppk_prefix_costs(eppk_ctx* ctx, const void* reqs, uint32_t n_reqs, const int32_t* lists, uint32_t k, const uint32_t* base,
+                      uint32_t unit, uint32_t* out_cost, uint32_t* out_matched);
+/* eppk_pick_costed[_device] charging the uncached blocks: on one stream the ordered fallbacks of eppk_pick_topk_device, the costs above
+ * over those lists into a buffer of the context, and eppk_costed_resolve_device(..., EPPK_COST_PER_ENTRY, ...).  d_cost of eppk_pick_costed
+ * becomes base (nullable) and unit; bands, caps, cap_all, loads in and out, ranks, SHED / SPILL and bad rows exactly as there (the host
+ * form checks base as eppk_pick_costed checks cost).  The buffer grows on demand, as the resolve's scratch does. */
+int eppk_pick_cost_cached_device(eppk_ctx* ctx, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, uint32_t k,
+                                   const uint32_t* d_base, uint32_t unit, const uint8_t* d_band, const eppk_band_table* bands,
+                                   const uint32_t* d_cap, uint32_t cap_all, uint32_t* d_load, int32_t* d_out_pick, double* d_out_score,
+                                   uint8_t* d_out_rank, void* stream);
+int eppk_pick_cost_cached(eppk_ctx* ctx, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t k,
+                            const uint32_t* base, uint32_t unit, const uint8_t* band, const eppk_band_table* bands, const uint32_t* cap,
+                            uint32_t cap_all, uint32_t* load, int32_t* out_pick, double* out_score, uint8_t* out_rank);
 
 /* ---- ... with fair shares between flows (SEMANTICS.md §3g) ---------------------------------------------------------------------
  * The entry points above decide who gets a pod's room by band first and inside a band by BATCH ORDER alone: one tenant whose requests
