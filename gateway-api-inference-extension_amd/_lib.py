@@ -18,6 +18,7 @@ EPPK_RANK_OVERFLOW, EPPK_RANK_NONE = 0x40, 0x80
 EPPK_MAX_BANDS = 8
 EPPK_MAX_COST = 0x00FFFFFF
 EPPK_COST_PER_ENTRY = 1
+EPPK_SCORE_SORT, EPPK_SCORE_WITHIN_LIST = 1, 2
 EPPK_MAX_FLOWS = 1024
 EPPK_SFAIR_MAX_REQS = 131072
 
@@ -43,6 +44,7 @@ SYMBOLS = [
     "eppk_banded_resolve_device", "eppk_pick_banded_device", "eppk_pick_banded", "eppk_group_pick_banded",
     "eppk_costed_resolve_device", "eppk_pick_costed_device", "eppk_pick_costed", "eppk_group_pick_costed",
     "eppk_prefix_costs_device", "eppk_prefix_costs", "eppk_pick_cost_cached_device", "eppk_pick_cost_cached",
+    "eppk_score_lists_device", "eppk_score_lists", "eppk_pick_rendezvous_scored_device", "eppk_pick_rendezvous_scored",
     "eppk_fair_resolve_device", "eppk_pick_fair_device", "eppk_pick_fair", "eppk_group_pick_fair",
     "eppk_wfair_resolve_device", "eppk_pick_wfair_device", "eppk_pick_wfair", "eppk_group_pick_wfair", "eppk_fair_turns_rebase",
     "eppk_sfair_resolve_device", "eppk_pick_sfair_device", "eppk_pick_sfair", "eppk_group_pick_sfair",
@@ -183,6 +185,10 @@ def load_library() -> C.CDLL:
     lib.eppk_group_pick_costed.argtypes = [vp, vp, u32, vp, u32, vp, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp]
     lib.eppk_prefix_costs_device.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, vp, vp]
     lib.eppk_prefix_costs.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, vp]
+    lib.eppk_score_lists_device.argtypes = [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp]
+    lib.eppk_score_lists.argtypes = [vp, vp, u32, vp, vp, u32, u32, vp, vp]
+    lib.eppk_pick_rendezvous_scored_device.argtypes = [vp, vp, u32, vp, u32, vp, vp, u32, u64, u32, vp, vp, vp]
+    lib.eppk_pick_rendezvous_scored.argtypes = [vp, vp, u32, vp, u32, vp, vp, u32, u64, u32, vp, vp]
     lib.eppk_pick_cost_cached_device.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp, vp]
     lib.eppk_pick_cost_cached.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp]
     lib.eppk_fair_resolve_device.argtypes = [vp, vp, vp, u32, u32, vp, u32, vp, u32, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp, vp]

@@ -17,6 +17,7 @@
 #include "eppk_sfair.hip.h"
 #include "eppk_rendezvous.hip.h"
 #include "eppk_prefix_costs.hip.h"
+#include "eppk_score_lists.hip.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -776,6 +777,46 @@ int launch_prefix_costs(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const 
   uint32_t n_pods = sn.n_pods;
   uint32_t* status = sn.status;
   void* args[] = {&nat, &n_pods, &status, &ix, &reqs8, &stride, &n_reqs, &d_lists, &k, &d_base, &unit, &d_cost, &d_matched};
+  HIPCHK(c, hipExtLaunchKernel(fn, dim3(grid), dim3(eppk::kPcThreads), args, 0, st, nullptr, nullptr, 0));
+  c->geom[0] = c->geom[1] = 0u; c->geom[2] = grid; c->geom[3] = eppk::kPcThreads;
+  c->last_done = nullptr;
+  c->last_stream = st;
+  return EPPK_OK;
+}
+
+// Chain totals of listed pods (SEMANTICS.md §3l): score_lists_kernel.  With a PREFIX scorer in the chain and an index the group is
+// prefix_costs_kernel's (lane = block); otherwise there is no walk and a request takes eight lanes.  Reads the index and the gauges:
+// ordered as a pick is.  The same persistent grid of 256-thread workgroups; always a launch.  d_pick may be d_lists.
+int launch_score_lists(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_mask, const int32_t* d_lists, uint32_t k, uint32_t flags,
+                       int32_t* d_pick, double* d_score, hipStream_t st) {
+  { const int rcf = learn_fence(c, st); if (rcf) return rcf; }
+  KSnap sn = make_ksnap(c);
+  KIndex ix = make_kindex(c);
+  KChain ch = c->kchain;
+  bool walk = false;
+  for (uint32_t s = 0; s < ch.n; ++s) walk |= ch.kind[s] == EPPK_SCORER_PREFIX;
+  walk = walk && ix.slots != 0u;
+  const uint32_t G = walk ? eppk::pc_group(c->cfg.max_blocks) : eppk::kSlNoWalkGroup;
+  const void* fn = nullptr;
+  by_lane_word(c, [&](auto tag) {
+    using LW = decltype(tag);
+    fn = !walk     ? (const void*)eppk::score_lists_kernel<LW, eppk::kSlNoWalkGroup, false>
+         : G == 16u ? (const void*)eppk::score_lists_kernel<LW, 16u, true>
+         : G == 32u ? (const void*)eppk::score_lists_kernel<LW, 32u, true>
+                    : (const void*)eppk::score_lists_kernel<LW, 64u, true>;
+    return 0;
+  });
+  const uint32_t wpb = eppk::kPcThreads / 64u, per_pass = 64u / G;
+  const uint32_t n_pass = (n_reqs + per_pass - 1u) / per_pass;
+  int occ_per_cu = 1;
+  { const int rco = occupancy_of(c, fn, eppk::kPcThreads, 0, &occ_per_cu); if (rco) return rco; }
+  uint32_t grid = (n_pass + wpb - 1u) / wpb;
+  const uint32_t cap = (uint32_t)c->num_cu * (uint32_t)occ_per_cu;
+  if (grid > cap) grid = cap;
+  if (grid < 1u) grid = 1u;
+  const uint8_t* reqs8 = (const uint8_t*)d_reqs;
+  uint32_t stride = c->stride;
+  void* args[] = {&sn, &ix, &ch, &reqs8, &stride, &n_reqs, &d_mask, &d_lists, &k, &flags, &d_pick, &d_score};
   HIPCHK(c, hipExtLaunchKernel(fn, dim3(grid), dim3(eppk::kPcThreads), args, 0, st, nullptr, nullptr, 0));
   c->geom[0] = c->geom[1] = 0u; c->geom[2] = grid; c->geom[3] = eppk::kPcThreads;
   c->last_done = nullptr;
@@ -3629,6 +3670,99 @@ int eppk_pick_cost_cached(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const 
                                return costed_resolve(c, c->d_tk_pick, c->d_tk_score, n_reqs, k, c->d_pc_cost, EPPK_COST_PER_ENTRY, band ? c->d_bn_band : nullptr, tab,
                                                      counts, d_cap, cap_all, d_load, d_pick, d_score, d_rank, c->stream);
                              });
+}
+
+// ---- chain totals of listed pods, ordered best first (SEMANTICS.md §3l; eppk_score_lists.hip.h) ------------------------------------
+
+namespace {
+
+int score_lists_check(eppk_ctx* c, const char* who, uint32_t k, uint32_t flags, const void* out_pick, const void* out_score) {
+  if (k < 1 || k > EPPK_MAX_TOPK) return fail(c, EPPK_ERR_ARG, std::string(who) + ": k out of range (1..8)");
+  if (flags & ~(EPPK_SCORE_SORT | EPPK_SCORE_WITHIN_LIST)) return fail(c, EPPK_ERR_ARG, std::string(who) + ": unknown flag bits");
+  if ((flags & EPPK_SCORE_SORT) ? !out_pick : !out_score)
+    return fail(c, EPPK_ERR_ARG, std::string(who) + ((flags & EPPK_SCORE_SORT) ? ": EPPK_SCORE_SORT needs out_pick" : ": no scores asked for (out_score NULL without EPPK_SCORE_SORT)"));
+  if (!c->have_snapshot) return fail(c, EPPK_ERR_NO_SNAPSHOT, std::string(who) + ": no snapshot published");
+  return EPPK_OK;
+}
+
+// The host forms' tail: the lists in d_tk_pick (uploaded, or written there by the rendezvous kernel) are scored in place (m: a mask is in d_tk_mask).
+int score_lists_host_finish(eppk_ctx* c, uint32_t n_reqs, bool m, uint32_t k, uint32_t flags, int32_t* out_pick, double* out_score) {
+  const int rc = launch_score_lists(c, c->d_tk_reqs, n_reqs, m ? (const uint64_t*)c->d_tk_mask : nullptr, c->d_tk_pick, k, flags, c->d_tk_pick, c->d_tk_score, c->stream);
+  if (rc) return rc;
+  if (out_pick) HIPCHK(c, hipMemcpyAsync(out_pick, c->d_tk_pick, (size_t)n_reqs * k * 4u, hipMemcpyDeviceToHost, c->stream));
+  if (out_score) HIPCHK(c, hipMemcpyAsync(out_score, c->d_tk_score, (size_t)n_reqs * k * 8u, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return EPPK_OK;
+}
+
+}  // namespace
+
+int eppk_score_lists_device(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, const int32_t* d_lists, uint32_t k, uint32_t flags,
+                            int32_t* d_out_pick, double* d_out_score, void* stream) {
+  if (!c || ((!d_reqs || !d_lists) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_score_lists_device: null argument");
+  const int rc = score_lists_check(c, "eppk_score_lists_device", k, flags, d_out_pick, d_out_score);
+  if (rc) return rc;
+  if (n_reqs == 0) return EPPK_OK;
+  if ((uint64_t)n_reqs * c->stride >= (1ull << 31)) return fail(c, EPPK_ERR_LIMIT, "eppk_score_lists_device: batch of 2 GiB and more (split it)");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  return launch_score_lists(c, d_reqs, n_reqs, c->n_pods ? d_cand_mask : nullptr, d_lists, k, flags, d_out_pick, d_out_score, stream ? (hipStream_t)stream : c->stream);
+}
+
+int eppk_score_lists(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, const int32_t* lists, uint32_t k, uint32_t flags,
+                     int32_t* out_pick, double* out_score) {
+  if (!c || ((!reqs || !lists) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_score_lists: null argument");
+  int rc = score_lists_check(c, "eppk_score_lists", k, flags, out_pick, out_score);
+  if (rc) return rc;
+  if (n_reqs > c->cfg.max_batch) return fail(c, EPPK_ERR_LIMIT, "eppk_score_lists: n_reqs > max_batch");
+  if (n_reqs == 0) return EPPK_OK;
+  if ((rc = validate_rows(c, "eppk_score_lists", reqs, n_reqs))) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if ((rc = topk_ensure(c, cand_mask != nullptr))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->d_tk_reqs, reqs, (size_t)n_reqs * c->stride, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_tk_pick, lists, (size_t)n_reqs * k * 4u, hipMemcpyHostToDevice, c->stream));
+  const size_t J = (c->n_pods + 63u) / 64u;
+  const bool m = cand_mask && J;
+  if (m) HIPCHK(c, hipMemcpyAsync(c->d_tk_mask, cand_mask, (size_t)n_reqs * J * 8u, hipMemcpyHostToDevice, c->stream));
+  return score_lists_host_finish(c, n_reqs, m, k, flags, out_pick, out_score);
+}
+
+// The k affinity pods of a request, best total first: the rendezvous kernel into the output, score_lists_kernel in place behind it.
+int eppk_pick_rendezvous_scored_device(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_key, uint32_t depth, const uint64_t* d_pod_key,
+                                       const uint64_t* d_cand_mask, uint32_t k, uint64_t seed, uint32_t flags, int32_t* d_out_pick, double* d_out_score,
+                                       void* stream) {
+  if (!c || ((!d_reqs || !d_out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_rendezvous_scored_device: null argument");
+  if (flags & ~(EPPK_SCORE_SORT | EPPK_SCORE_WITHIN_LIST)) return fail(c, EPPK_ERR_ARG, "eppk_pick_rendezvous_scored_device: unknown flag bits");
+  const int rc = eppk_pick_rendezvous_device(c, d_reqs, n_reqs, d_key, depth, d_pod_key, d_cand_mask, k, seed, d_out_pick, nullptr, stream);
+  if (rc) return rc;
+  return eppk_score_lists_device(c, d_reqs, n_reqs, d_cand_mask, d_out_pick, k, flags | EPPK_SCORE_SORT, d_out_pick, d_out_score, stream);
+}
+
+int eppk_pick_rendezvous_scored(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint64_t* key, uint32_t depth, const uint64_t* pod_key,
+                                const uint64_t* cand_mask, uint32_t k, uint64_t seed, uint32_t flags, int32_t* out_pick, double* out_score) {
+  if (!c || ((!reqs || !out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_rendezvous_scored: null argument");
+  if (k < 1 || k > EPPK_MAX_TOPK) return fail(c, EPPK_ERR_ARG, "eppk_pick_rendezvous_scored: k out of range (1..8)");
+  if (flags & ~(EPPK_SCORE_SORT | EPPK_SCORE_WITHIN_LIST)) return fail(c, EPPK_ERR_ARG, "eppk_pick_rendezvous_scored: unknown flag bits");
+  if (!key && depth == 0) return fail(c, EPPK_ERR_ARG, "eppk_pick_rendezvous_scored: neither keys nor a prefix depth");
+  if (!c->have_snapshot) return fail(c, EPPK_ERR_NO_SNAPSHOT, "eppk_pick_rendezvous_scored: no snapshot published");
+  if (n_reqs > c->cfg.max_batch) return fail(c, EPPK_ERR_LIMIT, "eppk_pick_rendezvous_scored: n_reqs > max_batch");
+  if (n_reqs == 0) return EPPK_OK;
+  int rc = validate_rows(c, "eppk_pick_rendezvous_scored", reqs, n_reqs);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const size_t J = (c->n_pods + 63u) / 64u;
+  const bool m = cand_mask && J;
+  rc = topk_ensure(c, cand_mask != nullptr);
+  if (!rc && key) rc = ctx_grow(c, c->cfg.max_batch, {{c->d_rv_key, 8u, "rendezvous keys"}});
+  if (!rc && pod_key) rc = ctx_grow(c, c->cfg.max_pods, {{c->d_rv_pod, 8u, "rendezvous pod keys"}});
+  if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->d_tk_reqs, reqs, (size_t)n_reqs * c->stride, hipMemcpyHostToDevice, c->stream));      // (the chain reads the rows in the session form too)
+  if (key) HIPCHK(c, hipMemcpyAsync(c->d_rv_key, key, (size_t)n_reqs * 8u, hipMemcpyHostToDevice, c->stream));
+  if (pod_key && c->n_pods) HIPCHK(c, hipMemcpyAsync(c->d_rv_pod, pod_key, (size_t)c->n_pods * 8u, hipMemcpyHostToDevice, c->stream));
+  if (m) HIPCHK(c, hipMemcpyAsync(c->d_tk_mask, cand_mask, (size_t)n_reqs * J * 8u, hipMemcpyHostToDevice, c->stream));
+  rc = launch_rendezvous(c, c->d_tk_reqs, n_reqs, key ? (const uint64_t*)c->d_rv_key : nullptr, depth, pod_key ? (const uint64_t*)c->d_rv_pod : nullptr,
+                         m ? (const uint64_t*)c->d_tk_mask : nullptr, k, seed, c->d_tk_pick, nullptr, c->stream);
+  if (rc) return rc;
+  return score_lists_host_finish(c, n_reqs, m, k, flags | EPPK_SCORE_SORT, out_pick, out_score);
 }
 
 // ---- ... with fair shares between flows (SEMANTICS.md §3g; eppk_fair.hip.h) ------------------------------------------------------

@@ -51,13 +51,79 @@ __device__ __forceinline__ uint32_t pc_group_bcast(uint32_t v, uint32_t lane) {
   } else if constexpr (G == 32u) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)v, (int)J), hi = (uint32_t)__builtin_amdgcn_readlane((int)v, (int)(32u + J));
     return lane < 32u ? lo : hi;
-  } else {
+  } else if constexpr (G == 16u) {
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x150 + (int)J, 0xf, 0xf, false);      // row_newbcast:J
+  } else {                                                                                          // G = 8 (score_lists_kernel): half a DPP row
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x150 + (int)J, 0xf, 0xf, false);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x158 + (int)J, 0xf, 0xf, false);
+    return (lane & 8u) ? hi : lo;
   }
 }
 template <uint32_t G, size_t... Js>
 __device__ __forceinline__ void pc_group_bcast_all(uint32_t v, uint32_t lane, uint32_t (&out)[EPPK_MAX_TOPK], std::index_sequence<Js...>) {
   ((out[Js] = pc_group_bcast<G, (uint32_t)Js>(v, lane)), ...);
+}
+
+// The block walk of one pass: lane gl of a group probes block t0 + gl of its request (`h` = that block's hash for the first trip, `row`
+// the request row for further ones, `nbe` the blocks the group walks: 0 = none) and returns, in lane j < k of the group, how many of the
+// leading hits hold pod P[j] (kPcNoPod: none).  Written once: prefix_costs_kernel and score_lists_kernel (eppk_score_lists.hip.h) call it.
+template <typename LW, uint32_t G>
+__device__ __forceinline__ uint32_t pc_walk(const KIndex& ix, const uint64_t* row, uint64_t h, uint32_t nbe, const uint32_t (&P)[EPPK_MAX_TOPK], const uint32_t k,
+                                            const uint32_t lane) {
+  constexpr uint64_t GM = G == 64u ? ~0ull : (1ull << (G & 63u)) - 1ull;
+  const uint32_t gl = lane & (G - 1u), gs = lane & ~(G - 1u);
+  auto grp = [&](uint64_t m) -> uint64_t { return G == 64u ? m : (m >> gs) & GM; };     // the lane's group's part of a ballot
+  uint32_t acc = 0u;
+  for (uint32_t t0 = 0u; __ballot(nbe > t0) != 0ull; t0 += G) {      // one trip unless G = 64 and a row is longer
+    const bool act = t0 + gl < nbe;
+    const uint32_t slot = probe(ix, h, act);
+    const uint64_t miss = grp(__ballot(act && slot == kNotFound));
+    const uint32_t nloc = nbe > t0 ? (nbe - t0 < G ? nbe - t0 : G) : 0u;
+    const uint32_t stop1 = miss ? (uint32_t)__builtin_ctzll(miss) : nloc;
+    const bool front = gl < stop1;
+    uint32_t d[16];
+    load_line16<false>(ix.lists_all + (size_t)(front ? slot : ix.slots + 2u) * kListDwords, d);      // (others: the all-zero row's empty line)
+    const uint32_t cnt = d[3];
+    const uint64_t empty = grp(__ballot(front && cnt == 0u));
+    const uint32_t stop = empty ? (uint32_t)__builtin_ctzll(empty) : stop1;
+    const uint64_t in_front = stop >= 64u ? ~0ull : (1ull << stop) - 1ull;      // group-relative
+    const uint64_t listed = __ballot(cnt - 1u < kListCap);
+    const uint64_t over = __ballot(front && cnt > kListCap);
+    uint64_t m[EPPK_MAX_TOPK];
+#pragma unroll
+    for (uint32_t j = 0; j < EPPK_MAX_TOPK; ++j) m[j] = 0ull;
+#pragma unroll
+    for (uint32_t c8 = 0; c8 < kListCap; c8 += 8u) {
+      if (c8 != 0u && __ballot(cnt > c8 && cnt <= kListCap) == 0ull) break;
+#pragma unroll
+      for (uint32_t e = 0; e < 8u; ++e) {
+        const uint32_t id = list_id(d, c8 + e);
+#pragma unroll
+        for (uint32_t j = 0; j < EPPK_MAX_TOPK; ++j)
+          if (j < k) m[j] |= __ballot(id == P[j]);
+      }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < EPPK_MAX_TOPK; ++j) m[j] &= listed;
+    if (__builtin_expect(over != 0ull, 0)) {                         // dense rows: the k words first, then their bits
+      const LW* bm = (const LW*)ix.bitmaps + (size_t)slot * 64u;
+      const bool mine = front && cnt > kListCap;
+      LW w[EPPK_MAX_TOPK];
+#pragma unroll
+      for (uint32_t j = 0; j < EPPK_MAX_TOPK; ++j) w[j] = (mine && j < k && P[j] != kPcNoPod) ? bm[P[j] & 63u] : (LW)0;
+#pragma unroll
+      for (uint32_t j = 0; j < EPPK_MAX_TOPK; ++j)
+        if (j < k) m[j] |= __ballot(((w[j] >> ((P[j] >> 6) & (8u * (uint32_t)sizeof(LW) - 1u))) & 1) != 0);
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < EPPK_MAX_TOPK; ++j) {
+      const uint32_t cj = (uint32_t)__builtin_popcountll(grp(m[j]) & in_front);
+      if (gl == j) acc += cj;
+    }
+    nbe = (stop == G && nbe > t0 + G) ? nbe : 0u;                    // every block of the trip hit and the row goes on
+    h = t0 + G + gl < nbe ? row[1u + t0 + G + gl] : 0ull;
+  }
+  return acc;
 }
 
 // What a pass needs of its request before anything can be probed (one request per group; r is clamped, a group past the batch is not stored).
@@ -69,12 +135,10 @@ __global__ __launch_bounds__(kPcThreads) void prefix_costs_kernel(const uint64_t
                                                                   const int32_t* __restrict__ lists, uint32_t k, const uint32_t* __restrict__ base,
                                                                   uint32_t unit, uint32_t* __restrict__ out_cost, uint32_t* __restrict__ out_matched) {
   constexpr uint32_t NG = 64u / G;                                     // requests per pass
-  constexpr uint64_t GM = G == 64u ? ~0ull : (1ull << (G & 63u)) - 1ull;
-  const uint32_t lane = threadIdx.x & 63u, gl = lane & (G - 1u), gs = lane & ~(G - 1u);
+  const uint32_t lane = threadIdx.x & 63u, gl = lane & (G - 1u);
   const uint32_t wib = threadIdx.x >> 6, wpb = blockDim.x >> 6;
   const uint32_t hwords = (stride - 8u) / 8u;
   const uint32_t n_pass = (n_reqs + NG - 1u) / NG, step = gridDim.x * wpb;
-  auto grp = [&](uint64_t m) -> uint64_t { return G == 64u ? m : (m >> gs) & GM; };     // the lane's group's part of a ballot
   auto fetch = [&](uint32_t q) -> PcFetch {
     const uint32_t r0 = q * NG + lane / G, r = r0 < n_reqs ? r0 : n_reqs - 1u;
     const uint64_t* row = (const uint64_t*)(reqs + (size_t)r * stride);
@@ -107,57 +171,7 @@ __global__ __launch_bounds__(kPcThreads) void prefix_costs_kernel(const uint64_t
     uint32_t P[EPPK_MAX_TOPK];
     pc_group_bcast_all<G>(pv, lane, P, std::make_index_sequence<EPPK_MAX_TOPK>{});
 
-    uint32_t acc = 0u;                                                 // matched[gl] of the lane's request
-    uint64_t h = cur.h;
-    for (uint32_t t0 = 0u; __ballot(nbe > t0) != 0ull; t0 += G) {      // one trip unless G = 64 and a row is longer
-      const bool act = t0 + gl < nbe;
-      const uint32_t slot = probe(ix, h, act);
-      const uint64_t miss = grp(__ballot(act && slot == kNotFound));
-      const uint32_t nloc = nbe > t0 ? (nbe - t0 < G ? nbe - t0 : G) : 0u;
-      const uint32_t stop1 = miss ? (uint32_t)__builtin_ctzll(miss) : nloc;
-      const bool front = gl < stop1;
-      uint32_t d[16];
-      load_line16<false>(ix.lists_all + (size_t)(front ? slot : ix.slots + 2u) * kListDwords, d);      // (others: the all-zero row's empty line)
-      const uint32_t cnt = d[3];
-      const uint64_t empty = grp(__ballot(front && cnt == 0u));
-      const uint32_t stop = empty ? (uint32_t)__builtin_ctzll(empty) : stop1;
-      const uint64_t in_front = stop >= 64u ? ~0ull : (1ull << stop) - 1ull;      // group-relative
-      const uint64_t listed = __ballot(cnt - 1u < kListCap);
-      const uint64_t over = __ballot(front && cnt > kListCap);
-      uint64_t m[EPPK_MAX_TOPK];
-#pragma unroll
-      for (uint32_t j = 0; j < EPPK_MAX_TOPK; ++j) m[j] = 0ull;
-#pragma unroll
-      for (uint32_t c8 = 0; c8 < kListCap; c8 += 8u) {
-        if (c8 != 0u && __ballot(cnt > c8 && cnt <= kListCap) == 0ull) break;
-#pragma unroll
-        for (uint32_t e = 0; e < 8u; ++e) {
-          const uint32_t id = list_id(d, c8 + e);
-#pragma unroll
-          for (uint32_t j = 0; j < EPPK_MAX_TOPK; ++j)
-            if (j < k) m[j] |= __ballot(id == P[j]);
-        }
-      }
-#pragma unroll
-      for (uint32_t j = 0; j < EPPK_MAX_TOPK; ++j) m[j] &= listed;
-      if (__builtin_expect(over != 0ull, 0)) {                         // dense rows: the k words first, then their bits
-        const LW* bm = (const LW*)ix.bitmaps + (size_t)slot * 64u;
-        const bool mine = front && cnt > kListCap;
-        LW w[EPPK_MAX_TOPK];
-#pragma unroll
-        for (uint32_t j = 0; j < EPPK_MAX_TOPK; ++j) w[j] = (mine && j < k && P[j] != kPcNoPod) ? bm[P[j] & 63u] : (LW)0;
-#pragma unroll
-        for (uint32_t j = 0; j < EPPK_MAX_TOPK; ++j)
-          if (j < k) m[j] |= __ballot(((w[j] >> ((P[j] >> 6) & (8u * (uint32_t)sizeof(LW) - 1u))) & 1) != 0);
-      }
-#pragma unroll
-      for (uint32_t j = 0; j < EPPK_MAX_TOPK; ++j) {
-        const uint32_t cj = (uint32_t)__builtin_popcountll(grp(m[j]) & in_front);
-        if (gl == j) acc += cj;
-      }
-      nbe = (stop == G && nbe > t0 + G) ? nbe : 0u;                    // every block of the trip hit and the row goes on
-      h = t0 + G + gl < nbe ? row[1u + t0 + G + gl] : 0ull;
-    }
+    const uint32_t acc = pc_walk<LW, G>(ix, row, cur.h, nbe, P, k, lane);     // matched[gl] of the lane's request
 
     if (live && gl < k) {
       uint32_t b = cur.base;

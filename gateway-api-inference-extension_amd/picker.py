@@ -816,6 +816,66 @@ class BatchedPicker:
         self._check(self._lib.eppk_prefix_costs_device(self._ctx, d_reqs, n_reqs, d_lists, int(k), d_base or None, int(unit), d_cost or None,
                                                        d_matched or None, stream or None), "prefix_costs_device")
 
+    # -- chain totals of listed pods, ordered best first (SEMANTICS.md §3l) ---------------------------
+    def _rows_and_mask(self, reqs: np.ndarray, mask: Optional[np.ndarray]):
+        reqs = np.ascontiguousarray(reqs, dtype=np.uint64)
+        assert reqs.ndim == 2 and reqs.shape[1] == self.row_words, "request row stride mismatch"
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint64)
+            assert mask.shape == (reqs.shape[0], (self.n_pods + 63) // 64), "mask shape mismatch"
+        return reqs, mask
+
+    def score_lists(self, reqs: np.ndarray, lists: np.ndarray, flags: int = 0, mask: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """eppk_score_lists: the chain's total of every valid entry of `lists` (i32 [R, k]) -- what pick_topk reports for that pair under
+        the same mask; EPPK_SCORE_WITHIN_LIST: the list is the candidate set -- and EPPK_NO_PICK / 0.0 for the others; EPPK_SCORE_SORT
+        orders each list best first.  ([R, k] pods, [R, k] totals)."""
+        reqs, mask = self._rows_and_mask(reqs, mask)
+        lists = np.ascontiguousarray(lists, dtype=np.int32)
+        R = reqs.shape[0]
+        assert lists.ndim == 2 and lists.shape[0] == R, "one list per request row"
+        k = lists.shape[1]
+        picks = np.full((R, k), -1, dtype=np.int32)
+        scores = np.zeros((R, k), dtype=np.float64)
+        self._check(self._lib.eppk_score_lists(self._ctx, reqs.ctypes.data, R, mask.ctypes.data if mask is not None else None, lists.ctypes.data, k,
+                                               int(flags), picks.ctypes.data, scores.ctypes.data), "score_lists")
+        return picks, scores
+
+    def score_lists_device(self, d_reqs: int, n_reqs: int, d_lists: int, k: int, flags: int, d_pick: Optional[int], d_score: Optional[int],
+                           d_mask: Optional[int] = None, stream: int = 0) -> None:
+        """eppk_score_lists_device: n_reqs * k entries at d_pick / d_score (d_pick may be d_lists), asynchronous on `stream`."""
+        self._check(self._lib.eppk_score_lists_device(self._ctx, d_reqs, n_reqs, d_mask or None, d_lists, int(k), int(flags), d_pick or None,
+                                                      d_score or None, stream or None), "score_lists_device")
+
+    def pick_rendezvous_scored(self, reqs: np.ndarray, k: int, seed: int, flags: int = 0, key: Optional[np.ndarray] = None, depth: int = 0,
+                               pod_key: Optional[np.ndarray] = None, mask: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """eppk_pick_rendezvous_scored: the k affinity pods of pick_rendezvous, best chain total first, with their totals."""
+        reqs, mask = self._rows_and_mask(reqs, mask)
+        R = reqs.shape[0]
+        kptr = pptr = None
+        if key is not None:
+            key = np.ascontiguousarray(key, dtype=np.uint64)
+            assert key.shape == (R,), "one key per request row"
+            kptr = key.ctypes.data
+        if pod_key is not None:
+            pod_key = np.ascontiguousarray(pod_key, dtype=np.uint64)
+            assert pod_key.shape == (self.n_pods,), "one key per published pod"
+            pptr = pod_key.ctypes.data
+        k = int(k)
+        picks = np.full((R, max(k, 0)), -1, dtype=np.int32)
+        scores = np.zeros((R, max(k, 0)), dtype=np.float64)
+        self._check(self._lib.eppk_pick_rendezvous_scored(self._ctx, reqs.ctypes.data, R, kptr, int(depth), pptr,
+                                                          mask.ctypes.data if mask is not None else None, k, seed & 0xFFFFFFFFFFFFFFFF, int(flags),
+                                                          picks.ctypes.data, scores.ctypes.data), "pick_rendezvous_scored")
+        return picks, scores
+
+    def pick_rendezvous_scored_device(self, d_reqs: int, n_reqs: int, k: int, seed: int, flags: int, d_pick: int, d_score: Optional[int],
+                                      d_key: Optional[int] = None, depth: int = 0, d_pod_key: Optional[int] = None, d_mask: Optional[int] = None,
+                                      stream: int = 0) -> None:
+        """eppk_pick_rendezvous_scored_device: n_reqs * k entries at d_pick / d_score, asynchronous on `stream` (0 = the context's)."""
+        self._check(self._lib.eppk_pick_rendezvous_scored_device(self._ctx, d_reqs, n_reqs, d_key or None, int(depth), d_pod_key or None, d_mask or None,
+                                                                 int(k), seed & 0xFFFFFFFFFFFFFFFF, int(flags), d_pick, d_score or None, stream or None),
+                    "pick_rendezvous_scored_device")
+
     def pick_costed_cached(self, reqs: np.ndarray, k: int, cap, unit: int = 1, base=None, bands=((_lib.EPPK_BOUNDED_SHED, 0),),
                            band: Optional[np.ndarray] = None, load: Optional[np.ndarray] = None, mask: Optional[np.ndarray] = None
                            ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray]]:

@@ -743,6 +743,49 @@ int eppk_pick_cost_cached(eppk_ctx* ctx, const void* reqs, uint32_t n_reqs, cons
                             const uint32_t* base, uint32_t unit, const uint8_t* band, const eppk_band_table* bands, const uint32_t* cap,
                             uint32_t cap_all, uint32_t* load, int32_t* out_pick, double* out_score, uint8_t* out_rank);
 
+/* ---- chain totals of listed pods, ordered best first (SEMANTICS.md §3l) --------------------------------------------------------
+ * The library produces candidate lists (eppk_pick_topk, eppk_pick_random_topk, eppk_pick_weighted_random, eppk_pick_rendezvous) and
+ * consumes them in the load resolves.  This call answers the question in between: what does the scorer chain say about the pods ON a
+ * list -- a rendezvous shortlist, a draw order, the caller's own sticky pod plus fallbacks?  For request row r, lists[r][0 .. k-1] with k
+ * in 1 .. EPPK_MAX_TOPK, and C(r) the request's candidates as every pick defines them (the mask row if given, AND active, AND < n_pods):
+ * entry j with p = lists[r][j] is VALID iff 0 <= p < n_pods and p is in C(r) (a hole, EPPK_NO_PICK, an id out of range and a pod outside the
+ * mask are invalid; a pod may appear twice, both entries are scored alike).  For a valid entry
+ *   total[r][j] = the total eppk_pick_batch / eppk_pick_topk report for the pair (r, p) under the same mask: SEMANTICS.md §2's sum in chain
+ *                 order, the QUEUE normalisers over C(r), PREFIX matched[p] over all pods.
+ *   EPPK_SCORE_WITHIN_LIST   C(r) is replaced by the valid entries of the list (Filter -> Score with the shortlist as the filter): the QUEUE
+ *                 normalisers are the minimum / maximum queue depth over the listed valid pods, one valid pod scores QUEUE 1.0, and the
+ *                 totals are those of eppk_pick_topk under a mask row with exactly those bits.
+ *   out_score[r][j] = total, out_pick[r][j] = p; an invalid entry gets EPPK_NO_PICK / 0.0.  Without EPPK_SCORE_SORT positions are kept,
+ *                 out_pick is nullable and out_score is not (EPPK_ERR_ARG).
+ *   EPPK_SCORE_SORT   out_pick is required, out_score nullable: the valid entries first in the order of eppk_pick_topk (total descending by
+ *                 binary64 compare, ties by pod index ascending, equal pods by list position), the invalid ones behind them.  The result is
+ *                 d_lists / d_list_scores of every resolve.
+ * d_out_pick == d_lists is allowed (in place).  A row out of range (n_blocks > max_blocks, adapter outside [-1, 128)): the host form
+ * refuses the batch with EPPK_ERR_ARG and names the lowest row; the device form writes EPPK_NO_PICK / 0.0 for the row and raises
+ * EPPK_LAUNCH_BAD_REQUEST_ROW.  EPPK_ERR_ARG: k out of range, unknown flag bits, null lists.  EPPK_ERR_NO_SNAPSHOT without a published
+ * snapshot.  EPPK_ERR_LIMIT: n_reqs > max_batch on the host form, a batch of 2 GiB and more on the device form.
+ * Always launches (also under EPPK_RESIDENT=1).  The device form is asynchronous on `stream` (NULL = the context's) and READS THE INDEX:
+ * the ordering rules are those of eppk_pick_batch_device.  Gauges are read as they stand -- the latest publish plus the assumed-load bumps
+ * taken so far; the call bumps nothing and is legal while eppk_set_assumed_load is on.  There is no group form: each member of a device
+ * group can call it on its shard.  Cost: DESIGN.md §3.21. */
+#define EPPK_SCORE_SORT        1u   /* reorder each list best first */
+#define EPPK_SCORE_WITHIN_LIST 2u   /* the list IS the candidate set */
+int eppk_score_lists_device(eppk_ctx* ctx, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, const int32_t* d_lists,
+                            uint32_t k, uint32_t flags, int32_t* d_out_pick, double* d_out_score, void* stream);
+int eppk_score_lists(eppk_ctx* ctx, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, const int32_t* lists, uint32_t k,
+                     uint32_t flags, int32_t* out_pick, double* out_score);
+/* The k affinity pods of a request, best total first: the arguments of eppk_pick_rendezvous[_device] plus `flags` (EPPK_SCORE_WITHIN_LIST
+ * or 0; EPPK_SCORE_SORT is implied).  On one stream the rendezvous kernel into d_out_pick, then eppk_score_lists_device in place: no
+ * context buffer on the device form.  The chain reads the request rows, so reqs is required in the session form too.  Errors and bad rows as
+ * the two calls; the result is d_lists / d_list_scores of every resolve: a small consistent shortlist, then the load-aware choice inside it
+ * (eppk_bounded_resolve_device(EPPK_BOUNDED_SPILL) behind it bounds the loads). */
+int eppk_pick_rendezvous_scored_device(eppk_ctx* ctx, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_key, uint32_t depth,
+                                       const uint64_t* d_pod_key, const uint64_t* d_cand_mask, uint32_t k, uint64_t seed, uint32_t flags,
+                                       int32_t* d_out_pick, double* d_out_score, void* stream);
+int eppk_pick_rendezvous_scored(eppk_ctx* ctx, const void* reqs, uint32_t n_reqs, const uint64_t* key, uint32_t depth,
+                                const uint64_t* pod_key, const uint64_t* cand_mask, uint32_t k, uint64_t seed, uint32_t flags,
+                                int32_t* out_pick, double* out_score);
+
 /* ---- ... with fair shares between flows (SEMANTICS.md §3g) ---------------------------------------------------------------------
  * The entry points above decide who gets a pod's room by band first and inside a band by BATCH ORDER alone: one tenant whose requests
  * sit at the front of a batch takes every slot of its band.  The reference names fairness between flows inside a priority band as
