@@ -18,6 +18,7 @@
 #include "eppk_rendezvous.hip.h"
 #include "eppk_prefix_costs.hip.h"
 #include "eppk_score_lists.hip.h"
+#include "eppk_index_export.hip.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -34,6 +35,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/eppk.h"
@@ -144,6 +146,8 @@ struct eppk_ctx {
   uint32_t sort_uses = 0;
   DBuf<eppk::IxLaunch> d_ixl;               // the capacity verdict of the insert launch in flight (index_budget_kernel)
   uint32_t index_epoch = 1;
+  DBuf<uint64_t> d_export;                  // scratch of the read-out (eppk_index_export.hip.h): pairs per 64-row tile, then per run of tiles; their offsets after the scan
+  HBuf<uint8_t> h_export;                   // pinned landing buffer of the host form (capacity: bytes): hashes | pods | ages
   DBuf<unsigned long long> stats;       // device [4 + kStatBanks*2*kStatSlots]: scratch, live keys, non-empty words, dropped inserts, then
                                         // banks of per-wave {hits, lookups}: consecutive launches use different banks, so pick
                                         // kernels overlapping on two streams never share a slot
@@ -1974,6 +1978,146 @@ int eppk_index_evict_older_device(eppk_ctx* c, uint32_t min_epoch, void* stream)
   }
   { const uint32_t horizon = min_epoch < c->index_epoch ? min_epoch : c->index_epoch; if (horizon > c->min_live) c->min_live = horizon; }
   return rc;
+}
+
+// ---- the index read out and restored (SEMANTICS.md §6d; eppk_index_export.hip.h) --------------------------------------------------
+
+namespace {
+uint32_t export_tiles(const eppk_ctx* c) { return c->slots ? (uint32_t)(((uint64_t)c->slots + 2u + 63u) / 64u) : 0u; }
+// a wavefront per tile, at most eight workgroups per CU: a larger table gives every wavefront more trips
+uint32_t export_grid(const eppk_ctx* c, uint32_t n_tiles) {
+  const uint32_t wg = (n_tiles * 64u + eppk::kExThreads - 1u) / eppk::kExThreads, full = (uint32_t)(c->num_cu > 0 ? c->num_cu : 1) * 8u;
+  return wg < full ? wg : full;
+}
+
+// Count pass and the two scan levels on `st`: *d_total = the triples of the index; d_export then holds every tile's offset inside its
+// run and every run's offset.  status (nullable): the sticky word to flag when cap != 0 holds fewer.
+int export_count(eppk_ctx* c, uint64_t cap, uint64_t* d_total, uint32_t* status, hipStream_t st) {
+  const uint32_t n_tiles = export_tiles(c), n_blocks = (n_tiles + eppk::kExScanTiles - 1u) / eppk::kExScanTiles;
+  if (n_tiles) {
+    const int rcg = ctx_grow(c, (size_t)n_tiles + n_blocks, {{c->d_export, 8u, "index export offsets"}});
+    if (rcg) return rcg;
+    const uint32_t grid = export_grid(c, n_tiles);
+    by_lane_word(c, [&](auto tag) {
+      using LW = decltype(tag);
+      hipLaunchKernelGGL((eppk::export_count_kernel<LW>), dim3(grid), dim3(eppk::kExThreads), 0, st, (const uint64_t*)c->keys, (const void*)c->bitmaps,
+                         (const uint32_t*)c->lists, c->slots, n_tiles, c->d_export.get());
+      return EPPK_OK;
+    });
+    hipLaunchKernelGGL(eppk::export_scan_tiles_kernel, dim3(n_blocks), dim3(eppk::kExScanThreads), 0, st, c->d_export.get(), n_tiles, c->d_export + n_tiles);
+  }
+  hipLaunchKernelGGL(eppk::export_scan_top_kernel, dim3(1), dim3(eppk::kExTopThreads), 0, st, n_tiles ? c->d_export + n_tiles : (uint64_t*)nullptr, n_blocks, cap,
+                     d_total, status);
+  HIPCHK(c, hipGetLastError());
+  return EPPK_OK;
+}
+
+// The scatter pass behind export_count on the same stream: the first `cap` triples of the order.
+int export_scatter(eppk_ctx* c, uint64_t* d_hashes, uint32_t* d_pods, uint8_t* d_ages, uint64_t cap, hipStream_t st) {
+  const uint32_t n_tiles = export_tiles(c);
+  if (!n_tiles || !cap) return EPPK_OK;
+  const uint32_t grid = export_grid(c, n_tiles);
+  by_lane_word(c, [&](auto tag) {
+    using LW = decltype(tag);
+    hipLaunchKernelGGL((eppk::export_scatter_kernel<LW>), dim3(grid), dim3(eppk::kExThreads), 0, st, (const uint64_t*)c->keys, (const void*)c->bitmaps,
+                       (const uint32_t*)c->lists, (const uint32_t*)c->rstamps, c->slots, c->index_epoch, eppk::tag_of_epoch(c->index_epoch), n_tiles, (const uint64_t*)c->d_export.get(),
+                       (const uint64_t*)(c->d_export + n_tiles), d_hashes, d_pods, d_ages, cap);
+    return EPPK_OK;
+  });
+  HIPCHK(c, hipGetLastError());
+  return EPPK_OK;
+}
+}  // namespace
+
+int eppk_index_export_device(eppk_ctx* c, uint64_t* d_hashes, uint32_t* d_pods, uint8_t* d_ages, uint64_t cap, uint64_t* d_total, void* stream) {
+  if (!c || !d_total || (cap && (!d_hashes || !d_pods || !d_ages))) return fail(c, EPPK_ERR_ARG, "eppk_index_export_device: null argument");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  { const int rcf = learn_fence(c, st); if (rcf) return rcf; }
+  const int rc = export_count(c, cap, d_total, c->d_status, st);
+  if (rc) return rc;
+  return export_scatter(c, d_hashes, d_pods, d_ages, cap, st);
+}
+
+int eppk_index_export(eppk_ctx* c, uint64_t* hashes, uint32_t* pods, uint8_t* ages, uint64_t cap, uint64_t* total) {
+  if (!c || !total || (cap && (!hashes || !pods || !ages))) return fail(c, EPPK_ERR_ARG, "eppk_index_export: null argument");
+  *total = 0;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  { const int rcf = learn_fence(c, c->stream); if (rcf) return rcf; }
+  // the count first: the staging is sized by what will be written, min(cap, total) triples, not by what the caller has room for
+  int rc = ctx_grow(c, 8u, {{c->d_tmp, 1u, "index staging"}});
+  if (rc) return rc;
+  rc = export_count(c, 0ull, (uint64_t*)c->d_tmp, nullptr, c->stream);
+  if (rc) return rc;
+  uint64_t all = 0;
+  HIPCHK(c, hipMemcpyAsync(&all, c->d_tmp, sizeof all, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *total = all;
+  const uint64_t n = all < cap ? all : cap;
+  if (n) {
+    const size_t bytes = (size_t)n * 13u, o_pod = (size_t)n * 8u, o_age = (size_t)n * 12u;      // hashes | pods | ages
+    if ((rc = ctx_grow(c, bytes, {{c->d_tmp, 1u, "index staging"}}))) return rc;
+    if ((rc = ctx_grow(c, bytes, {{c->h_export, 1u, "index export landing buffer"}}))) return rc;
+    uint8_t* d = (uint8_t*)c->d_tmp;
+    rc = export_scatter(c, (uint64_t*)d, (uint32_t*)(d + o_pod), d + o_age, n, c->stream);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->h_export.get(), d, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(hashes, c->h_export.get(), (size_t)n * 8u);
+    std::memcpy(pods, c->h_export + o_pod, (size_t)n * 4u);
+    std::memcpy(ages, c->h_export + o_age, (size_t)n);
+  }
+  if (cap && all > cap) return fail(c, EPPK_ERR_LIMIT, "eppk_index_export: the index holds " + std::to_string(all) + " triples, cap is " + std::to_string(cap));
+  return EPPK_OK;
+}
+
+int eppk_index_import(eppk_ctx* c, const uint64_t* hashes, const uint32_t* pods, const uint8_t* ages, uint64_t n, uint32_t* new_epoch) {
+  if (!c || ((!hashes || !pods || !ages) && n)) return fail(c, EPPK_ERR_ARG, "eppk_index_import: null argument");
+  if (new_epoch) *new_epoch = c->index_epoch;
+  if (n == 0) return EPPK_OK;
+  if (!c->slots) return fail(c, EPPK_ERR_ARG, "eppk_index_import: context was created with index_slots = 0");
+  // every check in front of the first insert: pods in range, ages inside the window, one age per hash
+  uint64_t per_age[kEpochWindow + 1u] = {0};
+  {
+    std::unordered_map<uint64_t, uint8_t> seen;
+    seen.reserve((size_t)n);
+    for (uint64_t i = 0; i < n; ++i) {
+      if (pods[i] >= c->cfg.max_pods) return fail(c, EPPK_ERR_LIMIT, "eppk_index_import: pod >= max_pods");
+      if (ages[i] > kEpochWindow) return fail(c, EPPK_ERR_ARG, "eppk_index_import: triple " + std::to_string(i) + " has an age beyond the window of 254 epochs");
+      const auto it = seen.emplace(hashes[i], ages[i]);
+      if (!it.second && it.first->second != ages[i])
+        return fail(c, EPPK_ERR_ARG, "eppk_index_import: triple " + std::to_string(i) + " gives its hash a second age (a hash has one stamp)");
+      ++per_age[ages[i]];
+    }
+  }
+  // grouped by age, oldest first (a counting sort that keeps the caller's order inside a group)
+  std::vector<uint64_t> gh((size_t)n);
+  std::vector<uint32_t> gp((size_t)n);
+  uint64_t first[kEpochWindow + 2u];
+  first[kEpochWindow + 1u] = 0;
+  for (uint32_t a = kEpochWindow + 1u; a-- > 0u;) first[a] = first[a + 1u] + per_age[a];      // first[a + 1] = where age a starts
+  {
+    uint64_t at[kEpochWindow + 1u];
+    for (uint32_t a = 0; a <= kEpochWindow; ++a) at[a] = first[a + 1u];
+    for (uint64_t i = 0; i < n; ++i) { const uint64_t j = at[ages[i]]++; gh[(size_t)j] = hashes[i]; gp[(size_t)j] = pods[i]; }
+  }
+  int full = EPPK_OK;                              // a group the table refused does not stop the ticks: what did go in keeps its age
+  uint32_t pending = 0;                            // the age of the group inserted last: the ticks still owed
+  bool any = false;
+  for (uint32_t a = kEpochWindow + 1u; a-- > 0u;) {
+    if (!per_age[a]) continue;
+    for (; any && pending > a; --pending) { const int rct = eppk_index_advance_epoch(c, nullptr); if (rct) return rct; }
+    any = true; pending = a;
+    for (uint64_t o = first[a + 1u]; o < first[a]; o += 1ull << 24) {
+      const uint32_t m = (uint32_t)std::min<uint64_t>(first[a] - o, 1ull << 24);
+      const int rci = eppk_index_insert(c, gh.data() + o, gp.data() + o, m);
+      if (rci == EPPK_ERR_INDEX_FULL) full = rci;
+      else if (rci) return rci;
+    }
+  }
+  for (; pending > 0u; --pending) { const int rct = eppk_index_advance_epoch(c, nullptr); if (rct) return rct; }
+  if (new_epoch) *new_epoch = c->index_epoch;
+  return full ? fail(c, full, "eppk_index_import: table at load limit, inserts dropped") : EPPK_OK;
 }
 
 // ---- the hot path ----------------------------------------------------------------------------------

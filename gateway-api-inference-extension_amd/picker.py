@@ -403,6 +403,26 @@ class BatchedPicker:
         self._check(self._lib.eppk_index_size(self._ctx, C.byref(n)), "index_size")
         return n.value
 
+    def index_export(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The index as (hashes u64, pods u32, ages u8), one entry per (hash, pod) pair, in table order (SEMANTICS.md §6d):
+        a count query, then the read-out.  hashes / pods feed index_insert unchanged, all three feed index_import."""
+        n = C.c_uint64(0)
+        self._check(self._lib.eppk_index_export(self._ctx, None, None, None, 0, C.byref(n)), "index_export (count)")
+        h, p, a = np.empty(n.value, np.uint64), np.empty(n.value, np.uint32), np.empty(n.value, np.uint8)
+        if n.value:
+            self._check(self._lib.eppk_index_export(self._ctx, h.ctypes.data, p.ctypes.data, a.ctypes.data, n.value, C.byref(n)), "index_export")
+        return h, p, a
+
+    def index_import(self, hashes: np.ndarray, pods: np.ndarray, ages: np.ndarray) -> int:
+        """Restore an export into this (fresh or cleared) index, ages included; returns the index epoch afterwards."""
+        h = np.ascontiguousarray(hashes, dtype=np.uint64).ravel()
+        p = np.ascontiguousarray(pods, dtype=np.uint32).ravel()
+        a = np.ascontiguousarray(ages, dtype=np.uint8).ravel()
+        assert h.shape == p.shape == a.shape
+        e = C.c_uint32(0)
+        self._check(self._lib.eppk_index_import(self._ctx, h.ctypes.data, p.ctypes.data, a.ctypes.data, h.shape[0], C.byref(e)), "index_import")
+        return e.value
+
     # -- the hot path -----------------------------------------------------------------------
     def pick(self, reqs: np.ndarray, mask: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
         """Host-buffer entry point. reqs: [R, 1+max_blocks] u64 rows; mask: [R, ceil(P/64)] u64 or None."""

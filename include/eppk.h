@@ -213,6 +213,31 @@ int eppk_index_trim_pods(eppk_ctx* ctx, uint32_t cap_per_pod, uint64_t* n_remove
  * behind the inserts and ahead of the next pick, without draining the pipeline.  eppk_index_size reports the effect.  Also valid while
  * staging sets of the pipelined host path are in flight (eppk_pick_stage_begin, below): ordered behind their picks and updates. */
 int eppk_index_evict_older_device(eppk_ctx* ctx, uint32_t min_epoch, void* stream);
+/* The index read out (SEMANTICS.md §6d): one (hash, pod, age) triple per member of every present hash's pod set.  hashes[i] / pods[i]
+ * are laid out as eppk_index_insert takes them; ages[i] = index epoch - the hash's stamp, exact in 0 .. EPPK_INDEX_EPOCH_WINDOW (not the
+ * capped age of eppk_index_trim_pods).  *total always receives the number of triples in the index; cap = 0 with NULL arrays is the count
+ * query.  With total > cap the first `cap` triples of the order are written and nothing behind them, and the host form returns
+ * EPPK_ERR_LIMIT (*total is valid).
+ * Order: ascending physical row of the table (the rows of the reserved hashes 0 and ~0 last), pods ascending inside a hash.  It is
+ * deterministic -- one index state, one sequence of bytes -- but NOT stable across an import or between two contexts: where a hash
+ * lives depends on the history of inserts and evictions.  Compare exports as sorted triples.
+ * Evicted hashes and removed pods are not exported; a pod that is a hole was removed at publish.  Valid with index_slots = 0 (total 0).
+ * Read-only, ordered like every other index call of the context: behind whatever updated the index, by one stream or by events.  The
+ * host form is synchronous on the context's stream; the device form takes DEVICE pointers (d_total too), is asynchronous on `stream`
+ * (NULL = the context's) and reports total > cap (cap != 0) through eppk_launch_status: EPPK_LAUNCH_EXPORT_TRUNCATED.
+ * A member of a device group is read through eppk_group_ctx(g, i). */
+int eppk_index_export_device(eppk_ctx* ctx, uint64_t* d_hashes, uint32_t* d_pods, uint8_t* d_ages, uint64_t cap, uint64_t* d_total, void* stream);
+int eppk_index_export(eppk_ctx* ctx, uint64_t* hashes, uint32_t* pods, uint8_t* ages, uint64_t cap, uint64_t* total);
+/* The way back in, meant for a FRESH or CLEARED index (a restarted gateway, a second replica, a context with a larger index_slots):
+ * the triples are grouped by age, the oldest group is inserted as eppk_index_insert does, the epoch advances by the gap to the next
+ * group's age, and so on until the age-0 group is in (the epoch advances by the LARGEST imported age in all; *new_epoch, nullable,
+ * receives it).  Afterwards an imported hash of age a has age a here.  What the index held before has aged by the largest imported age,
+ * under the window above: the ticks evict what grows older than 254 epochs.
+ * Capacity, holes and pods as in eppk_index_insert: pod >= max_pods is EPPK_ERR_LIMIT, a hole is ignored, EPPK_ERR_INDEX_FULL is passed
+ * through (the remaining groups and ticks still run, so what went in has its age).  The ages of one hash must agree -- a hash has one
+ * stamp -- and every age must be <= EPPK_INDEX_EPOCH_WINDOW: otherwise EPPK_ERR_ARG, checked on the host before the first insert, and
+ * nothing is inserted.  Synchronous.  A group member is restored through eppk_group_ctx(g, i). */
+int eppk_index_import(eppk_ctx* ctx, const uint64_t* hashes, const uint32_t* pods, const uint8_t* ages, uint64_t n, uint32_t* new_epoch);
 
 /* ---- the hot path --------------------------------------------------------------------------- */
 
@@ -343,6 +368,7 @@ int eppk_pick_learn_device(eppk_ctx* ctx, const void* d_reqs, uint32_t n_reqs, c
                                           * hang the device): that (hash, pod) pair was dropped */
 #define EPPK_LAUNCH_LEARN_FAILED    8u   /* eppk_pick_stage_begin(EPPK_PICK_LEARN) launched the picks but could not enqueue the post-route index
                                           * update behind them (eppk_last_error says why): the picks were delivered, the index did not learn them */
+#define EPPK_LAUNCH_EXPORT_TRUNCATED 16u /* eppk_index_export_device: the index held more triples than `cap`; the first `cap` were written */
 /* Synchronise the device and return (and clear) the sticky launch-status flags accumulated by every *_device launch of this
  * context since the last call.  0 = every row was in range. */
 int eppk_launch_status(eppk_ctx* ctx, uint32_t* flags);
