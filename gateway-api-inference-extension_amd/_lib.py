@@ -45,6 +45,7 @@ SYMBOLS = [
     "eppk_costed_resolve_device", "eppk_pick_costed_device", "eppk_pick_costed", "eppk_group_pick_costed",
     "eppk_prefix_costs_device", "eppk_prefix_costs", "eppk_pick_cost_cached_device", "eppk_pick_cost_cached",
     "eppk_score_lists_device", "eppk_score_lists", "eppk_pick_rendezvous_scored_device", "eppk_pick_rendezvous_scored",
+    "eppk_prefix_summary_device", "eppk_prefix_summary", "eppk_pick_hybrid_device", "eppk_pick_hybrid",
     "eppk_fair_resolve_device", "eppk_pick_fair_device", "eppk_pick_fair", "eppk_group_pick_fair",
     "eppk_wfair_resolve_device", "eppk_pick_wfair_device", "eppk_pick_wfair", "eppk_group_pick_wfair", "eppk_fair_turns_rebase",
     "eppk_sfair_resolve_device", "eppk_pick_sfair_device", "eppk_pick_sfair", "eppk_group_pick_sfair",
@@ -192,6 +193,10 @@ def load_library() -> C.CDLL:
     lib.eppk_score_lists.argtypes = [vp, vp, u32, vp, vp, u32, u32, vp, vp]
     lib.eppk_pick_rendezvous_scored_device.argtypes = [vp, vp, u32, vp, u32, vp, vp, u32, u64, u32, vp, vp, vp]
     lib.eppk_pick_rendezvous_scored.argtypes = [vp, vp, u32, vp, u32, vp, vp, u32, u64, u32, vp, vp]
+    lib.eppk_prefix_summary_device.argtypes = [vp, vp, u32, vp, vp, vp]
+    lib.eppk_prefix_summary.argtypes = [vp, vp, u32, vp, vp]
+    lib.eppk_pick_hybrid_device.argtypes = [vp, vp, u32, vp, u32, vp, vp, u32, u64, u32, vp, vp, vp, vp]
+    lib.eppk_pick_hybrid.argtypes = [vp, vp, u32, vp, u32, vp, vp, u32, u64, u32, vp, vp, vp]
     lib.eppk_pick_cost_cached_device.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp, vp]
     lib.eppk_pick_cost_cached.argtypes = [vp, vp, u32, vp, u32, vp, u32, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp]
     lib.eppk_fair_resolve_device.argtypes = [vp, vp, vp, u32, u32, vp, u32, vp, u32, vp, C.POINTER(BandTable), vp, u32, vp, vp, vp, vp, vp]

@@ -18,6 +18,7 @@
 #include "eppk_rendezvous.hip.h"
 #include "eppk_prefix_costs.hip.h"
 #include "eppk_score_lists.hip.h"
+#include "eppk_prefix_summary.hip.h"
 #include "eppk_index_export.hip.h"
 
 #include <hip/hip_runtime.h>
@@ -257,6 +258,8 @@ struct eppk_ctx {
   DBuf<uint32_t> d_pc_base;                                 // [rows] the full costs a host form uploads
   DBuf<uint32_t> d_pc_cost;                                 // [rows][EPPK_MAX_TOPK] costs: what eppk_pick_cost_cached hands its resolve
   DBuf<uint32_t> d_pc_matched;                              // [rows][EPPK_MAX_TOPK] matched blocks (host form)
+  // prefix-hit summary and the hybrid pick (SEMANTICS.md §3m; eppk_prefix_summary.hip.h): kHybridRowBytes per row, laid out per call
+  DBuf<uint8_t> d_hy;                                       // summaries [n][4] u32 | cold scores [n][k] f64 | cold picks [n][k] i32 | route bytes [n] (host form)
 
   // measurement
   bool prof = false;
@@ -823,6 +826,38 @@ int launch_score_lists(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const u
   void* args[] = {&sn, &ix, &ch, &reqs8, &stride, &n_reqs, &d_mask, &d_lists, &k, &flags, &d_pick, &d_score};
   HIPCHK(c, hipExtLaunchKernel(fn, dim3(grid), dim3(eppk::kPcThreads), args, 0, st, nullptr, nullptr, 0));
   c->geom[0] = c->geom[1] = 0u; c->geom[2] = grid; c->geom[3] = eppk::kPcThreads;
+  c->last_done = nullptr;
+  c->last_stream = st;
+  return EPPK_OK;
+}
+
+// The prefix-hit summary (SEMANTICS.md §3m): prefix_summary_kernel, a wavefront per request.  Reads the index: ordered behind a LEARN
+// batch's update as a pick is.  A persistent grid of 256-thread workgroups, as many as fit the CUs this context may use; always a launch.
+int launch_prefix_summary(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_mask, uint32_t* d_out, hipStream_t st) {
+  { const int rcf = learn_fence(c, st); if (rcf) return rcf; }
+  const void* fn = nullptr;
+  by_lane_word(c, [&](auto tag) {
+    using LW = decltype(tag);
+    fn = (const void*)eppk::prefix_summary_kernel<LW>;
+    return 0;
+  });
+  KSnap sn = make_ksnap(c);
+  KIndex ix = make_kindex(c);
+  const uint32_t wpb = eppk::kPsThreads / 64u;
+  int occ_per_cu = 1;
+  { const int rco = occupancy_of(c, fn, eppk::kPsThreads, 0, &occ_per_cu); if (rco) return rco; }
+  uint32_t grid = (n_reqs + wpb - 1u) / wpb;
+  const uint32_t cap = (uint32_t)c->num_cu * (uint32_t)occ_per_cu;
+  if (grid > cap) grid = cap;
+  if (grid < 1u) grid = 1u;
+  const uint8_t* reqs8 = (const uint8_t*)d_reqs;
+  uint32_t stride = c->stride;
+  const void* act_t = sn.act_t;
+  uint32_t n_pods = sn.n_pods;
+  uint32_t* status = sn.status;
+  void* args[] = {&act_t, &n_pods, &status, &ix, &reqs8, &stride, &n_reqs, &d_mask, &d_out};
+  HIPCHK(c, hipExtLaunchKernel(fn, dim3(grid), dim3(eppk::kPsThreads), args, 0, st, nullptr, nullptr, 0));
+  c->geom[0] = c->geom[1] = 0u; c->geom[2] = grid; c->geom[3] = eppk::kPsThreads;
   c->last_done = nullptr;
   c->last_stream = st;
   return EPPK_OK;
@@ -3907,6 +3942,120 @@ int eppk_pick_rendezvous_scored(eppk_ctx* c, const void* reqs, uint32_t n_reqs, 
                          m ? (const uint64_t*)c->d_tk_mask : nullptr, k, seed, c->d_tk_pick, nullptr, c->stream);
   if (rc) return rc;
   return score_lists_host_finish(c, n_reqs, m, k, flags | EPPK_SCORE_SORT, out_pick, out_score);
+}
+
+// ---- the prefix-hit summary per request and the hybrid pick built on it (SEMANTICS.md §3m; eppk_prefix_summary.hip.h) ----------------
+
+namespace {
+
+constexpr size_t kHybridRowBytes = 16u + EPPK_MAX_TOPK * (8u + 4u) + 1u;      // eppk_ctx::d_hy: a summary, a cold list's scores, its picks, a host form's route byte
+
+int hybrid_scratch(eppk_ctx* c, uint32_t n_reqs) { return ctx_grow(c, bounded_rows(c, n_reqs), {{c->d_hy, kHybridRowBytes, "prefix summary and hybrid pick: scratch"}}); }
+
+int hybrid_check(eppk_ctx* c, const char* who, uint32_t depth, bool keyed, uint32_t k, uint32_t min_hit) {
+  if (k < 1 || k > EPPK_MAX_TOPK) return fail(c, EPPK_ERR_ARG, std::string(who) + ": k out of range (1..8)");
+  if (min_hit < 1) return fail(c, EPPK_ERR_ARG, std::string(who) + ": min_hit 0 (matched blocks that make a row warm, >= 1)");
+  if (!keyed && depth == 0) return fail(c, EPPK_ERR_ARG, std::string(who) + ": neither keys nor a prefix depth");
+  if (!c->have_snapshot) return fail(c, EPPK_ERR_NO_SNAPSHOT, std::string(who) + ": no snapshot published");
+  return EPPK_OK;
+}
+
+// The three passes and the select behind them, all on `st`: the summary into d_hy, the ordered fallbacks into d_pick / d_score, the k
+// affinity pods by total into d_hy; the select moves the cold rows' entries over.  `stream` is st as the caller gave it (NULL = the context's).
+int hybrid_run(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_key, uint32_t depth, const uint64_t* d_pod_key, const uint64_t* d_mask,
+               uint32_t k, uint64_t seed, uint32_t min_hit, int32_t* d_pick, double* d_score, uint8_t* d_route, void* stream) {
+  int rc = hybrid_scratch(c, n_reqs);
+  if (rc) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  uint32_t* d_sum = (uint32_t*)c->d_hy.get();
+  double* cold_score = (double*)(c->d_hy.get() + (size_t)n_reqs * 16u);
+  int32_t* cold_pick = (int32_t*)(c->d_hy.get() + (size_t)n_reqs * (16u + (size_t)k * 8u));
+  if ((rc = launch_prefix_summary(c, d_reqs, n_reqs, c->n_pods ? d_mask : nullptr, d_sum, st))) return rc;
+  if ((rc = eppk_pick_topk_device(c, d_reqs, n_reqs, d_mask, k, d_pick, d_score, stream))) return rc;
+  if ((rc = eppk_pick_rendezvous_scored_device(c, d_reqs, n_reqs, d_key, depth, d_pod_key, d_mask, k, seed, 0u, cold_pick, cold_score, stream))) return rc;
+  const uint32_t n = n_reqs * k, threads = 256u;
+  hipLaunchKernelGGL(eppk::hybrid_select_kernel, dim3((n + threads - 1u) / threads), dim3(threads), 0, st, (const uint4*)d_sum, min_hit, n_reqs, k,
+                     (const int32_t*)cold_pick, (const double*)cold_score, d_pick, d_score, d_route);
+  HIPCHK(c, hipGetLastError());
+  return EPPK_OK;
+}
+
+}  // namespace
+
+int eppk_prefix_summary_device(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, uint32_t* d_out, void* stream) {
+  if (!c || ((!d_reqs || !d_out) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_prefix_summary_device: null argument");
+  if (!c->have_snapshot) return fail(c, EPPK_ERR_NO_SNAPSHOT, "eppk_prefix_summary_device: no snapshot published");
+  if (n_reqs == 0) return EPPK_OK;
+  if ((uint64_t)n_reqs * c->stride >= (1ull << 31)) return fail(c, EPPK_ERR_LIMIT, "eppk_prefix_summary_device: batch of 2 GiB and more (split it)");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  return launch_prefix_summary(c, d_reqs, n_reqs, c->n_pods ? d_cand_mask : nullptr, d_out, stream ? (hipStream_t)stream : c->stream);
+}
+
+int eppk_prefix_summary(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t* out) {
+  if (!c || ((!reqs || !out) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_prefix_summary: null argument");
+  if (!c->have_snapshot) return fail(c, EPPK_ERR_NO_SNAPSHOT, "eppk_prefix_summary: no snapshot published");
+  if (n_reqs > c->cfg.max_batch) return fail(c, EPPK_ERR_LIMIT, "eppk_prefix_summary: n_reqs > max_batch");
+  if (n_reqs == 0) return EPPK_OK;
+  int rc = validate_rows(c, "eppk_prefix_summary", reqs, n_reqs);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const size_t J = (c->n_pods + 63u) / 64u;
+  const bool m = cand_mask && J;
+  if ((rc = topk_ensure(c, cand_mask != nullptr))) return rc;
+  if ((rc = hybrid_scratch(c, n_reqs))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->d_tk_reqs, reqs, (size_t)n_reqs * c->stride, hipMemcpyHostToDevice, c->stream));
+  if (m) HIPCHK(c, hipMemcpyAsync(c->d_tk_mask, cand_mask, (size_t)n_reqs * J * 8u, hipMemcpyHostToDevice, c->stream));
+  if ((rc = launch_prefix_summary(c, c->d_tk_reqs, n_reqs, m ? (const uint64_t*)c->d_tk_mask : nullptr, (uint32_t*)c->d_hy.get(), c->stream))) return rc;
+  HIPCHK(c, hipMemcpyAsync(out, c->d_hy, (size_t)n_reqs * 16u, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return EPPK_OK;
+}
+
+int eppk_pick_hybrid_device(eppk_ctx* c, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_key, uint32_t depth, const uint64_t* d_pod_key,
+                            const uint64_t* d_cand_mask, uint32_t k, uint64_t seed, uint32_t min_hit, int32_t* d_out_pick, double* d_out_score,
+                            uint8_t* d_route, void* stream) {
+  if (!c || ((!d_reqs || !d_out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_hybrid_device: null argument");
+  const int rc = hybrid_check(c, "eppk_pick_hybrid_device", depth, d_key != nullptr, k, min_hit);
+  if (rc) return rc;
+  if (n_reqs == 0) return EPPK_OK;
+  if ((uint64_t)n_reqs * c->stride >= (1ull << 31)) return fail(c, EPPK_ERR_LIMIT, "eppk_pick_hybrid_device: batch of 2 GiB and more (split it)");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  return hybrid_run(c, d_reqs, n_reqs, d_key, depth, d_pod_key, d_cand_mask, k, seed, min_hit, d_out_pick, d_out_score, d_route, stream);
+}
+
+int eppk_pick_hybrid(eppk_ctx* c, const void* reqs, uint32_t n_reqs, const uint64_t* key, uint32_t depth, const uint64_t* pod_key, const uint64_t* cand_mask,
+                     uint32_t k, uint64_t seed, uint32_t min_hit, int32_t* out_pick, double* out_score, uint8_t* route) {
+  if (!c || ((!reqs || !out_pick) && n_reqs)) return fail(c, EPPK_ERR_ARG, "eppk_pick_hybrid: null argument");
+  int rc = hybrid_check(c, "eppk_pick_hybrid", depth, key != nullptr, k, min_hit);
+  if (rc) return rc;
+  if (n_reqs > c->cfg.max_batch) return fail(c, EPPK_ERR_LIMIT, "eppk_pick_hybrid: n_reqs > max_batch");
+  if (n_reqs == 0) return EPPK_OK;
+  if ((rc = validate_rows(c, "eppk_pick_hybrid", reqs, n_reqs))) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const size_t J = (c->n_pods + 63u) / 64u;
+  if (cand_mask && !J) {                             // a mask over no pods: nobody is a candidate, nothing matches, every row is cold
+    for (size_t i = 0; i < (size_t)n_reqs * k; ++i) { out_pick[i] = EPPK_NO_PICK; if (out_score) out_score[i] = 0.0; }
+    if (route) std::memset(route, 0, n_reqs);
+    return EPPK_OK;
+  }
+  rc = topk_ensure(c, cand_mask != nullptr);
+  if (!rc) rc = hybrid_scratch(c, n_reqs);
+  if (!rc && key) rc = ctx_grow(c, c->cfg.max_batch, {{c->d_rv_key, 8u, "rendezvous keys"}});
+  if (!rc && pod_key) rc = ctx_grow(c, c->cfg.max_pods, {{c->d_rv_pod, 8u, "rendezvous pod keys"}});
+  if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->d_tk_reqs, reqs, (size_t)n_reqs * c->stride, hipMemcpyHostToDevice, c->stream));
+  if (key) HIPCHK(c, hipMemcpyAsync(c->d_rv_key, key, (size_t)n_reqs * 8u, hipMemcpyHostToDevice, c->stream));
+  if (pod_key && c->n_pods) HIPCHK(c, hipMemcpyAsync(c->d_rv_pod, pod_key, (size_t)c->n_pods * 8u, hipMemcpyHostToDevice, c->stream));
+  if (cand_mask) HIPCHK(c, hipMemcpyAsync(c->d_tk_mask, cand_mask, (size_t)n_reqs * J * 8u, hipMemcpyHostToDevice, c->stream));
+  uint8_t* d_route = route ? c->d_hy.get() + (size_t)n_reqs * (16u + (size_t)k * 12u) : nullptr;      // (behind what hybrid_run lays out)
+  if ((rc = hybrid_run(c, c->d_tk_reqs, n_reqs, key ? (const uint64_t*)c->d_rv_key : nullptr, depth, pod_key ? (const uint64_t*)c->d_rv_pod : nullptr,
+                       cand_mask ? (const uint64_t*)c->d_tk_mask : nullptr, k, seed, min_hit, c->d_tk_pick, c->d_tk_score, d_route, nullptr)))
+    return rc;
+  HIPCHK(c, hipMemcpyAsync(out_pick, c->d_tk_pick, (size_t)n_reqs * k * 4u, hipMemcpyDeviceToHost, c->stream));
+  if (out_score) HIPCHK(c, hipMemcpyAsync(out_score, c->d_tk_score, (size_t)n_reqs * k * 8u, hipMemcpyDeviceToHost, c->stream));
+  if (route) HIPCHK(c, hipMemcpyAsync(route, d_route, n_reqs, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return EPPK_OK;
 }
 
 // ---- ... with fair shares between flows (SEMANTICS.md §3g; eppk_fair.hip.h) ------------------------------------------------------

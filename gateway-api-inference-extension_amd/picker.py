@@ -896,6 +896,52 @@ class BatchedPicker:
                                                                  int(k), seed & 0xFFFFFFFFFFFFFFFF, int(flags), d_pick, d_score or None, stream or None),
                     "pick_rendezvous_scored_device")
 
+    # -- the prefix-hit summary per request and the hybrid pick (SEMANTICS.md §3m) ---------------------
+    def prefix_summary(self, reqs: np.ndarray, mask: Optional[np.ndarray] = None) -> np.ndarray:
+        """eppk_prefix_summary: per request row {walk, best, holders, first} ([R, 4] u32) -- the leading blocks the index holds, the
+        most of them any candidate holds, how many candidates hold that many, and the lowest of those (0xFFFFFFFF: none)."""
+        reqs, mask = self._rows_and_mask(reqs, mask)
+        out = np.zeros((reqs.shape[0], 4), dtype=np.uint32)
+        self._check(self._lib.eppk_prefix_summary(self._ctx, reqs.ctypes.data, reqs.shape[0], mask.ctypes.data if mask is not None else None,
+                                                  out.ctypes.data), "prefix_summary")
+        return out
+
+    def prefix_summary_device(self, d_reqs: int, n_reqs: int, d_out: int, d_mask: Optional[int] = None, stream: int = 0) -> None:
+        """eppk_prefix_summary_device: n_reqs * 4 u32 at d_out (16-byte aligned), asynchronous on `stream` (0 = the context's)."""
+        self._check(self._lib.eppk_prefix_summary_device(self._ctx, d_reqs, n_reqs, d_mask or None, d_out, stream or None), "prefix_summary_device")
+
+    def pick_hybrid(self, reqs: np.ndarray, k: int, seed: int, min_hit: int, key: Optional[np.ndarray] = None, depth: int = 0,
+                    pod_key: Optional[np.ndarray] = None, mask: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """eppk_pick_hybrid: a row whose best candidate holds at least `min_hit` leading blocks gets pick_topk's row (route 1), every
+        other row pick_rendezvous_scored's (route 0).  ([R, k] pods, [R, k] totals, [R] u8 routes)."""
+        reqs, mask = self._rows_and_mask(reqs, mask)
+        R = reqs.shape[0]
+        kptr = pptr = None
+        if key is not None:
+            key = np.ascontiguousarray(key, dtype=np.uint64)
+            assert key.shape == (R,), "one key per request row"
+            kptr = key.ctypes.data
+        if pod_key is not None:
+            pod_key = np.ascontiguousarray(pod_key, dtype=np.uint64)
+            assert pod_key.shape == (self.n_pods,), "one key per published pod"
+            pptr = pod_key.ctypes.data
+        k = int(k)
+        picks = np.full((R, max(k, 0)), -1, dtype=np.int32)
+        scores = np.zeros((R, max(k, 0)), dtype=np.float64)
+        route = np.zeros(R, dtype=np.uint8)
+        self._check(self._lib.eppk_pick_hybrid(self._ctx, reqs.ctypes.data, R, kptr, int(depth), pptr, mask.ctypes.data if mask is not None else None, k,
+                                               seed & 0xFFFFFFFFFFFFFFFF, int(min_hit), picks.ctypes.data, scores.ctypes.data, route.ctypes.data),
+                    "pick_hybrid")
+        return picks, scores, route
+
+    def pick_hybrid_device(self, d_reqs: int, n_reqs: int, k: int, seed: int, min_hit: int, d_pick: int, d_score: Optional[int],
+                           d_route: Optional[int] = None, d_key: Optional[int] = None, depth: int = 0, d_pod_key: Optional[int] = None,
+                           d_mask: Optional[int] = None, stream: int = 0) -> None:
+        """eppk_pick_hybrid_device: n_reqs * k entries at d_pick / d_score, n_reqs bytes at d_route, asynchronous on `stream`."""
+        self._check(self._lib.eppk_pick_hybrid_device(self._ctx, d_reqs, n_reqs, d_key or None, int(depth), d_pod_key or None, d_mask or None, int(k),
+                                                      seed & 0xFFFFFFFFFFFFFFFF, int(min_hit), d_pick, d_score or None, d_route or None, stream or None),
+                    "pick_hybrid_device")
+
     def pick_costed_cached(self, reqs: np.ndarray, k: int, cap, unit: int = 1, base=None, bands=((_lib.EPPK_BOUNDED_SHED, 0),),
                            band: Optional[np.ndarray] = None, load: Optional[np.ndarray] = None, mask: Optional[np.ndarray] = None
                            ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray]]:

@@ -812,6 +812,42 @@ int eppk_pick_rendezvous_scored(eppk_ctx* ctx, const void* reqs, uint32_t n_reqs
                                 const uint64_t* pod_key, const uint64_t* cand_mask, uint32_t k, uint64_t seed, uint32_t flags,
                                 int32_t* out_pick, double* out_score);
 
+/* ---- what the index knows about a request, and the warm / cold route built on it (SEMANTICS.md §3m) -----------------------------------
+ * eppk_prefix_costs answers for the at most 8 pods on a list, and the picks fold matched[p] into a total.  This call answers for EVERY
+ * candidate: does the request's best candidate hold 11 of its 12 blocks, or does nobody hold anything?  For request row r, C(r) its
+ * candidates as every pick defines them (the mask row if given, AND active, AND < n_pods) and matched[p] exactly the PREFIX scorer's
+ * (SEMANTICS.md §3: over all pods, the walk stops at the first block whose set is absent or empty), out[r] is four u32 words (out: 16-byte
+ * aligned, [n_reqs][4]):
+ *   [0] walk     the number of leading blocks whose set is non-empty: the length of that walk.  Does not depend on the mask.
+ *   [1] best     max over p in C(r) of matched[p]; 0 when C(r) is empty or nothing matched.
+ *   [2] holders  |{p in C(r) : matched[p] == best}| if best > 0, else 0.
+ *   [3] first    the lowest such p if best > 0, else 0xFFFFFFFF.
+ * n_blocks - best is the uncached suffix (does a separate prefill pod pay?), best / n_blocks the prefix-hit ratio, holders whether a hit is
+ * exclusive.  A row out of range (n_blocks > max_blocks, adapter outside [-1, 128)): the host form refuses the batch with EPPK_ERR_ARG and
+ * names the lowest row; the device form writes {0, 0, 0, 0xFFFFFFFF} for the row and raises EPPK_LAUNCH_BAD_REQUEST_ROW.  A context with
+ * index_slots = 0 gives that record for every row.  EPPK_ERR_NO_SNAPSHOT without a published snapshot.  EPPK_ERR_LIMIT: n_reqs > max_batch on
+ * the host form, a batch of 2 GiB and more on the device form.  The device form is asynchronous on `stream` (NULL = the context's) and
+ * READS THE INDEX: the ordering rules are those of eppk_pick_batch_device.  Reads no gauge, bumps nothing, legal while
+ * eppk_set_assumed_load is on; always launches (also under EPPK_RESIDENT=1).  There is no group form: a member of a device group is reached
+ * through eppk_group_ctx(g, i).  Cost: DESIGN.md §3.23. */
+int eppk_prefix_summary_device(eppk_ctx* ctx, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_cand_mask, uint32_t* d_out, void* stream);
+int eppk_prefix_summary(eppk_ctx* ctx, const void* reqs, uint32_t n_reqs, const uint64_t* cand_mask, uint32_t* out);
+/* The hybrid pick: "when scheduling a request with low or no prefix cache in the index, use the consistent hashing strategy".  The arguments
+ * of eppk_pick_rendezvous_scored[_device] without `flags`, then
+ *   min_hit   >= 1 (0: EPPK_ERR_ARG, nothing is written): row r is WARM iff best[r] >= min_hit, best as above under the same mask.
+ *   route     nullable u8 [n_reqs]: 1 for a warm row, 0 for a cold or a bad one.
+ * A warm row's k entries and scores are byte for byte its row of eppk_pick_topk for the batch; a cold row's are byte for byte its row of
+ * eppk_pick_rendezvous_scored with flags = 0 (the k affinity pods, best total first); a row out of range is EPPK_NO_PICK / 0.0 on the
+ * device form (EPPK_LAUNCH_BAD_REQUEST_ROW) and refuses the batch on the host form.  The result is d_lists / d_list_scores of every
+ * resolve.  On one stream: the summary, the ordered fallbacks into the outputs, the rendezvous-scored pass into a buffer of the context
+ * (grown on demand, as the resolves' scratch), and a select pass.  Errors, ordering and side effects are those of the calls it is made of. */
+int eppk_pick_hybrid_device(eppk_ctx* ctx, const void* d_reqs, uint32_t n_reqs, const uint64_t* d_key, uint32_t depth,
+                            const uint64_t* d_pod_key, const uint64_t* d_cand_mask, uint32_t k, uint64_t seed, uint32_t min_hit,
+                            int32_t* d_out_pick, double* d_out_score, uint8_t* d_route, void* stream);
+int eppk_pick_hybrid(eppk_ctx* ctx, const void* reqs, uint32_t n_reqs, const uint64_t* key, uint32_t depth, const uint64_t* pod_key,
+                     const uint64_t* cand_mask, uint32_t k, uint64_t seed, uint32_t min_hit, int32_t* out_pick, double* out_score,
+                     uint8_t* route);
+
 /* ---- ... with fair shares between flows (SEMANTICS.md §3g) ---------------------------------------------------------------------
  * The entry points above decide who gets a pod's room by band first and inside a band by BATCH ORDER alone: one tenant whose requests
  * sit at the front of a batch takes every slot of its band.  The reference names fairness between flows inside a priority band as
